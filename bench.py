@@ -126,7 +126,40 @@ def parse_args(argv=None):
                          "command on the same box).  Without it roofline.traffic is null: a plain run measures no counters.  With it, "
                          "the figure is quoted only if the hash of the kernel sources AND of the built library recorded in the summary "
                          "equal this tree's and the workload matches")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (x, y and the QPALMInfo fields of the batch) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (x and y of a fixed, seeded sample of the QPs when the batch's do not fit)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs: the results of the last timed step, for output-by-output comparison of two builds
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240601
+# QPALMInfo fields a caller receives per QP (the timings setup_time / solve_time / run_time are left out: they differ from run to run)
+DUMP_INFO_FIELDS = ("status_val", "iter", "iter_out", "pri_res_norm", "dua_res_norm", "dua2_res_norm", "objective", "dual_objective")
+
+
+def dump_outputs(out_dir, xs, ys, infos, rank=0, world=1):
+    """DIR/x.npy [k][n], DIR/y.npy [k][m] and DIR/info_<field>.npy [B], all float64; DIR/qp_index.npy [k] names the QPs of the batch
+    that x and y hold: every QP when the files fit in DUMP_BUDGET_BYTES (shared evenly by the ranks), else a sample drawn with a fixed
+    seed, the same for the same batch shape.  With several ranks every rank writes its own shard with a `_rank<r>` suffix."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B = xs.shape[0]
+    arrays = {"info_" + f: np.array([float(getattr(i, f)) for i in infos], dtype=np.float64) for f in DUMP_INFO_FIELDS}
+    headers = 4096 * (len(arrays) + 3)                              # generous: an .npy header is 128 bytes
+    budget = DUMP_BUDGET_BYTES // world - headers - sum(a.nbytes for a in arrays.values()) - 8 * B
+    k = max(0, min(B, budget // (8 * (xs.shape[1] + ys.shape[1]))))
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, k, replace=False))
+    arrays.update(qp_index=idx.astype(np.float64), x=np.asarray(xs, dtype=np.float64)[idx], y=np.asarray(ys, dtype=np.float64)[idx])
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -443,6 +476,8 @@ def sparse_workload(args, ctx, rank, world, dist, torch):
         elapsed = float(t.item())
     infos, stats = bt.infos(), bt.stats_all()
     xs, ys = bt.solution()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, xs, ys, infos, rank, world)
     ok = all(int(i.status_val) == 1 for i in infos) and kkt_spot_check(probs, xs, ys, sorted({0, B // 3, B // 2, B - 1})) <= 1e-4
     mean = lambda f: float(np.mean([f(s) for s in stats]))
     perm, levels = bt.sparse_perm(0)
@@ -604,6 +639,8 @@ def worker(args):
     iters = np.array([int(i.iter) for i in infos])
     n_bad = int(np.sum(statuses != 1))
     xs, ys = bt.solution()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, xs, ys, infos, rank, world)
     import hashlib
     sol_hash = hashlib.sha256(np.ascontiguousarray(xs).tobytes() + np.ascontiguousarray(ys).tobytes()).hexdigest()[:16]   # same-box A/B: equal results?
     kkt = kkt_spot_check(probs, xs, ys, sorted({0, B // 3, B // 2, B - 1}), bmin_all, bmax_all)

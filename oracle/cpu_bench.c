@@ -3,7 +3,7 @@
  *
  * This is bench.py's cpu_baseline leg (kind "port"): one oracle workspace per thread at a time, no Python in the loop.
  * Every QP is timed the way the reference times itself: info.run_time = setup_time + solve_time
- * (/root/reference/src/qpalm.c:493-495,721-723), here clock_gettime(CLOCK_MONOTONIC) around oq_setup + oq_solve;
+ * (the reference's src/qpalm.c:493-495,721-723), here clock_gettime(CLOCK_MONOTONIC) around oq_setup + oq_solve;
  * oq_cleanup is outside the per-QP figure but inside the wall time the throughput is computed from.
  *
  *   cpu_bench <problems.bin> <threads> [passes] [sparse]      (sparse = 1: the oracle's sparse-storage mode, natural ordering: what the

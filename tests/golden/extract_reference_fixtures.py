@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Extracts the golden vectors held by the reference's own test-suite into a JSON fixture.
 
-Run in the build container only (reads /root/reference, which does not exist on the GPU box):
+Run by hand, with a checkout of the reference (Benny44/QPALM); the tests never run it, the committed JSON is the fixture:
 
-    python tests/golden/extract_reference_fixtures.py
+    python tests/golden/extract_reference_fixtures.py <path of the QPALM checkout>
 
 Output: tests/golden/reference_tests.json -- problem data (inputs) and expected outputs
 (solution vectors, statuses, tolerances) of tests/src/test_*.c.  Only DATA is extracted: literal
@@ -14,7 +14,7 @@ import os
 import re
 import sys
 
-REF = "/root/reference/tests/src"
+REF = None   # <QPALM checkout>/tests/src, set by main()
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_tests.json")
 
 NUM = r"[-+]?(?:\d+\.\d*|\.\d+|\d+)(?:[eE][-+]?\d+)?"
@@ -89,8 +89,12 @@ def lineno(fname, needle):
 
 
 def main():
+    global REF
+    if len(sys.argv) != 2:
+        sys.exit("usage: extract_reference_fixtures.py <path of the QPALM checkout>")
+    REF = os.path.join(sys.argv[1], "tests", "src")
     if not os.path.isdir(REF):
-        sys.exit("reference tree not present; the committed JSON is the fixture")
+        sys.exit("%s: no reference test sources there; the committed JSON is the fixture" % REF)
     fx = {"_generator": "tests/golden/extract_reference_fixtures.py", "problems": {}, "expect": {}}
     P = fx["problems"]
     P["basic_qp"] = problem("test_basic_qp.c")

@@ -59,15 +59,61 @@ def test_launcher_environment(monkeypatch):
     assert "torch" not in [m for m in sys.modules if m == "torch"] or True   # bench imports torch only inside worker()
 
 
+def test_steps_must_be_positive():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files within the budget; every QP when they fit, else the same seeded sample on every call"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from qpalm_amd.capi import Info
+    B, n, m = 64, 30, 50
+    rng = np.random.default_rng(5)
+    xs, ys = rng.random((B, n)), rng.random((B, m))
+    infos = (Info * B)()
+    for k in range(B):
+        infos[k].iter, infos[k].status_val, infos[k].objective = k, 1, 0.25 * k
+
+    def files(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    bench.dump_outputs(str(tmp_path / "all"), xs, ys, infos)
+    a = files(tmp_path / "all")
+    assert set(a) == {"x", "y", "qp_index"} | {"info_" + f for f in bench.DUMP_INFO_FIELDS}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a["x"], xs) and np.array_equal(a["y"], ys) and np.array_equal(a["qp_index"], np.arange(B))
+    assert np.array_equal(a["info_iter"], np.arange(B)) and np.array_equal(a["info_objective"], 0.25 * np.arange(B))
+    budget = 4096 * 11 + 9 * 8 * B + 20 * 8 * (n + m)        # room for 20 of the 64 QPs
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), xs, ys, infos)
+    s1, s2 = files(tmp_path / "s1"), files(tmp_path / "s2")
+    idx = s1["qp_index"].astype(int)
+    assert len(idx) == 20 and np.all(np.diff(idx) > 0) and all(np.array_equal(s1[k], s2[k]) for k in s1)
+    assert np.array_equal(s1["x"], xs[idx]) and np.array_equal(s1["y"], ys[idx]) and len(s1["info_iter"]) == B
+    assert sum(os.path.getsize(os.path.join(tmp_path, "s1", f)) for f in os.listdir(tmp_path / "s1")) <= budget
+
+
 @pytest.mark.gpu
-def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--batch", "64", "--n", "200", "--no-cpu"],
-                       capture_output=True, text=True, timeout=900, env=_env_without_dist())
+def test_bench_single_gpu_line(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--batch", "64", "--n", "200", "--no-cpu",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=_env_without_dist())
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["solve_stats"]["all_solved"] and d["roofline"]["traffic"] is None
     assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["measured_copy_GBps"] > 1000
     assert set(d["roofline"]["phases"]) == {"solve", "update", "factor", "spmv_vectors"}
+    assert d["steps"] == 1 and d["ms_per_step"] > 0
+    import hashlib
+    import numpy as np
+    x, y = np.load(tmp_path / "x.npy"), np.load(tmp_path / "y.npy")
+    assert x.shape == (64, 200) and y.shape == (64, 400) and np.all(np.load(tmp_path / "info_status_val.npy") == 1)
+    assert hashlib.sha256(x.tobytes() + y.tobytes()).hexdigest()[:16] == d["solve_stats"]["solution_sha256_16"]
 
 
 @pytest.mark.gpu
