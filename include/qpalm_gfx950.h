@@ -154,6 +154,11 @@ void qpg_ctx_destroy(qpg_ctx *ctx);
  *   "queue_order"           1 (default) = a launch of more QPs than resident slots starts the members in descending order of the kernel time of
  *                           their previous solve (the launch's tail is then made of short solves); 0 = index order.  Never changes a result.
  *   "sparse_factor", "sparse_ordering"   the sparse L D L' and its ordering (qpg_batch_sparse_info / qpg_batch_sparse_perm below)
+ *   "sparse_kkt"            0 (default) = a batch created with factorization_method = FACTORIZE_KKT keeps the dense (n+m) x (n+m) panel (more than 8192
+ *                           rows are refused); 1 = it keeps a sparse L D L' of K on the pattern of K_full (every row of A), ordered by nested
+ *                           dissection with the dense rows of A last ("sparse_ordering" -1 / 1; 0 = the natural [x; y]), whatever its size, with
+ *                           sparse row additions / deletions (ladel_row_add / ladel_row_del) and the reference's refactorise-or-update rule.
+ *                           Fixed when the batch is created.  enable_dual_termination and nonconvex are refused (QPG_ERR_UNSUPPORTED)
  *   "sparse_gpw"            columns of a level a wavefront of the sparse factorisation takes at a time: 1, 2, 4 or 8 groups of 64 / gpw lanes (default 8,
  *                           halved while the work vectors of all resident factors would exceed 4 GB).  Never changes a result.
  *   "sparse_lds"            1 (default) = the sparse factorisation accumulates a column, the sparse solves keep the right-hand side and the path
@@ -205,9 +210,12 @@ int  qpg_batch_launch_shape(qpg_batch *bt, qpg_int *workgroups, qpg_int *threads
  * Where its policy is not the reference's: rows that enter or leave the active set, and rows whose penalty changed
  * (ldlupdate_sigma_changed, solver_interface.c:443-503), are rank-1 updates along their elimination-tree paths only while
  * 2 x changed rows x tree height < n; beyond that the factor is rebuilt (on a chain-like tree -- a band under the natural ordering --
- * a path is the whole matrix).  QPGStats.n_refactor / n_rank1 then differ from the reference's split; the matrices factorised do not. */
+ * a path is the whole matrix).  QPGStats.n_refactor / n_rank1 then differ from the reference's split; the matrices factorised do not.
+ * KKT mode under "sparse_kkt" = 1: the sparse L D L' of K (n + m rows); the refactorise-or-update rule is the reference's (newton.c:32-53) and
+ * n_rank1 counts row additions + deletions as on the dense KKT panel. */
 int  qpg_batch_sparse_info(qpg_batch *bt, qpg_int idx, qpg_int *nnzL, qpg_int *device_bytes);
-/* The ordering of member idx's sparse factor, P H P' = L D L': perm[new] = old (n entries), and the height of its elimination tree.
+/* The ordering of member idx's sparse factor, P H P' = L D L': perm[new] = old (n entries; KKT mode under "sparse_kkt": P K P', n + m entries
+ * in the [x; y] numbering, nested dissection unless "sparse_ordering" = 0), and the height of its elimination tree.
  * The reference configures CHOLMOD_NATURAL (solver_interface.c:530-540: identity); context option "sparse_ordering" = 1 orders by
  * nested dissection instead, -1 (default) does so where the natural tree is deep (a band: one column per level) and dissection makes it
  * at least four times shallower -- the factorisation and the solves run at the latency of the tree's height.  Changes rounding, not
@@ -251,7 +259,9 @@ int qpg_set_active_constraints(qpg_batch *bt, qpg_int idx);
 int qpg_exact_linesearch(qpg_batch *bt, qpg_int idx, qpg_float *tau);
 /* ---- the KKT operations of solver_interface.h (batches created with factorization_method = FACTORIZE_KKT; QPG_ERR_UNSUPPORTED
  * otherwise).  State as in the reference: active_constraints, enter / leave lists with nb_enter / nb_leave, sigma_inv, gamma,
- * dphi; the (n+m) x (n+m) panel and sol_kkt / rhs_kkt live on the device ("L", "Dfac", "sol_kkt", "kkt_state"). ---- */
+ * dphi; the (n+m) x (n+m) panel and sol_kkt / rhs_kkt live on the device ("L", "Dfac", "sol_kkt", "kkt_state").  With the context option
+ * "sparse_kkt" = 1 the same five operations work on the sparse L D L' of K: qpg_kkt_form then records every constraint's state from the active
+ * set (kkt_state 1 / 0) and qpg_kkt_factorize assembles K from those states inside the sparse factorisation. ---- */
 /* qpalm_form_kkt / qpalm_reform_kkt (solver_interface.h:82,89; solver_interface.c:119-200): K = [[Q + I/gamma, A_a'], [A_a, -Sigma_a^-1]]
  * for the current active set into the slot (lower triangle; inactive constraints = unit diagonal), not factorised */
 int qpg_kkt_form(qpg_batch *bt, qpg_int idx);

@@ -133,6 +133,8 @@ struct qpg_ctx {
                               -1 (default): dissection where the natural tree is deep and the dissected one at least four times shallower */
   int sparse_factor;       /* -1 (default): the sparse L D L' (qpalm_sparse.h) for factors of more than 8192 rows, the dense panel otherwise; 1: sparse
                               whenever the mode allows it (Schur path); 0: never (larger factors are refused) */
+  int sparse_kkt;          /* 0 (default): FACTORIZE_KKT keeps the dense (n+m) x (n+m) panel (more than 8192 rows are refused); 1: every KKT batch keeps a
+                              sparse L D L' of K (qpalm_sparse_kkt.h), whatever its size */
   int ld_align;            /* leading dimension of the factor panels = rows rounded up to this many doubles.  16 (default): every column starts on a
                               128-byte line of the L2, so a wavefront's 1 KB column segment is 8 whole lines; with 8 (rounds 1-3) the odd columns of the
                               n = 1000 panel started mid-line and every segment touched 9 (measured: DESIGN section 4, round 4) */
@@ -195,7 +197,7 @@ extern "C" int qpg_ctx_create(int device, qpg_ctx **out) {
   std::string why;
   if (RT_DEVICE_INIT(device, why) != 0) return fail(QPG_ERR_NO_DEVICE, "qpg_ctx_create: " + why);
   qpg_ctx *c = new qpg_ctx();
-  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->sparse_factor = -1; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
+  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->sparse_factor = -1; c->sparse_kkt = 0; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
   for (int k = 0; k < 5; k++) { c->mv_buf[k] = nullptr; c->mv_cap[k] = 0; }
   *out = c;
   return api_ok();
@@ -234,6 +236,7 @@ extern "C" int qpg_ctx_set_option(qpg_ctx *ctx, const char *name, qpg_int value)
   else if (!strcmp(name, "sweep_ranks")) { if (value != 16 && value != 32) return fail(QPG_ERR_INVALID, "sweep_ranks must be 16 or 32"); ctx->sweep_ranks = (int)value; }
   else if (!strcmp(name, "kkt_compact")) ctx->kkt_compact = value ? 1 : 0;
   else if (!strcmp(name, "sparse_factor")) ctx->sparse_factor = (value < 0) ? -1 : (value ? 1 : 0);
+  else if (!strcmp(name, "sparse_kkt")) ctx->sparse_kkt = value ? 1 : 0;
   else if (!strcmp(name, "sequential_rank_sums")) ctx->sequential_rank_sums = (value < 0) ? -1 : (value ? 1 : 0);
   else if (!strcmp(name, "linesearch_hbm")) ctx->linesearch_hbm = (value < 0) ? 0 : (int)std::min<qpg_int>(value, 1 << 20); /* >= 2: also caps the tile (a power of two): small QPs then exercise several tiles and the HBM steps between them */
   else if (!strcmp(name, "sparse_gpw")) ctx->sparse_gpw = (int)value;
@@ -269,10 +272,16 @@ extern "C" int qpg_batch_create(qpg_ctx *ctx, qpg_int B, qpg_int n, qpg_int m, q
   const int kkt = (settings->factorization_method == 0) ? 1 : 0;
   const qpg_int nfac = kkt ? n + m : n;
   /* Factors of more than 8192 rows (the dense panel's limit: its right-hand side must fit the LDS) are kept as a sparse L D L'
-   * (qpalm_sparse.h; round 5) -- Schur path only (round 6: with the second resident factor of dual termination); "sparse_factor" = 1
-   * selects it for any size.  (The reference decides per matrix inside CHOLMOD; here the mode is fixed when the batch is created,
+   * (qpalm_sparse.h; round 5) on the Schur path (round 6: with the second resident factor of dual termination); "sparse_factor" = 1
+   * selects it for any size.  KKT mode keeps the dense panel unless "sparse_kkt" = 1 asks for the sparse factor of K (qpalm_sparse_kkt.h),
+   * whatever the size.  (The reference decides per matrix inside CHOLMOD; here the mode is fixed when the batch is created,
    * before the patterns are known, because the device arena is sized then.) */
-  const int sparse = (!kkt && (ctx->sparse_factor == 1 || (ctx->sparse_factor != 0 && nfac > 8192))) ? 1 : 0;
+  const int sparse = kkt ? ctx->sparse_kkt : ((ctx->sparse_factor == 1 || (ctx->sparse_factor != 0 && nfac > 8192)) ? 1 : 0);
+  /* the sparse factor of K (option "sparse_kkt") has no LD_Q on K's pattern and no lobpcg / Gershgorin bound of its own */
+  if (kkt && sparse && settings->enable_dual_termination)
+    return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_create: the sparse KKT factor does not support enable_dual_termination (no LD_Q on the pattern of K)");
+  if (kkt && sparse && settings->nonconvex)
+    return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_create: the sparse KKT factor does not support nonconvex");
   if (nfac > 8192 && !sparse)
     return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_create: the factor exceeds the dense-panel limit of 8192 rows (the sparse factor covers the Schur path)");
   /* up to 4 QP_T rows the update sweep keeps its running vectors in registers (k_solve<1|2|4>); larger factors (up to the
@@ -611,21 +620,24 @@ struct SparseSym {
   int nlev;
   bool dissected;
 };
-/* Nested dissection of the graph of H = Q + A'A (George's automatic scheme on breadth-first level structures): a band-like pattern,
+/* Nested dissection (sparse_order, below) of the graph of H = Q + A'A or of K (sparse_adj_H / sparse_adj_K; George's automatic scheme on breadth-first level structures): a band-like pattern,
  * whose elimination tree under the natural ordering is a chain of n columns (one column per level: the factorisation and the solves
  * then run at the latency of n dependent steps), becomes a tree of height ~ leaf + separator x log2(n / leaf) whose levels hold
  * hundreds of independent columns.  Vertices of very high degree (dense rows / columns: an arrow's shaft) are set aside and ordered last;
  * the rest is split recursively: connected components one after the other; a component by the middle level of the level structure
  * rooted at a pseudo-peripheral vertex (first half, second half, separator last); small pieces keep their natural order.  The
  * reference configures CHOLMOD_NATURAL; this is an engine option that changes speed and rounding, not what is computed. */
-static void sparse_order(const qpg_batch *bt, size_t b, std::vector<int> &perm) {
+/* the graph a factor's ordering works on: neighbours of every vertex (original numbering, no self loops) */
+struct SparseAdj { std::vector<int> p, i; };
+/* graph of H = Q + A'A (a long row of A -- a clique of H whatever the ordering -- enters as a chain of its columns: ordering quality only) */
+static void sparse_adj_H(const qpg_batch *bt, size_t b, SparseAdj &G) {
   const HostProblem &P = bt->probs[b];
   const int n = P.n;
   const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
   const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
-  const int LEAF = 24, LONG_ROW = 64;
-  /* adjacency (a long row of A -- a clique of H whatever the ordering -- enters as a chain of its columns: ordering quality only) */
-  std::vector<int> adjp((size_t)n + 1, 0), adji, mark((size_t)n, -1);
+  const int LONG_ROW = 64;
+  std::vector<int> &adjp = G.p, &adji = G.i, mark((size_t)n, -1);
+  adjp.assign((size_t)n + 1, 0); adji.clear();
   for (int j = 0; j < n; j++) {
     mark[j] = j;
     for (int k = Qfp[j]; k < Qfp[j + 1]; k++) { const int i = Qfi[k]; if (mark[i] != j) { mark[i] = j; adji.push_back(i); } }
@@ -639,6 +651,30 @@ static void sparse_order(const qpg_batch *bt, size_t b, std::vector<int> &perm) 
     }
     adjp[j + 1] = (int)adji.size();
   }
+}
+/* graph of K_full = [[Q + I, A'], [A, I]] with ALL rows of A (the reference's kkt_full): vertices 0 .. n-1 the variables, n + k constraint k.
+ * A superset of every active set's K, so the factor's structure never changes when rows enter or leave */
+static void sparse_adj_K(const qpg_batch *bt, size_t b, SparseAdj &G) {
+  const HostProblem &P = bt->probs[b];
+  const int n = P.n, m = P.m;
+  const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
+  const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
+  std::vector<int> &adjp = G.p, &adji = G.i, mark((size_t)n, -1);
+  adjp.assign((size_t)n + m + 1, 0); adji.clear();
+  for (int j = 0; j < n; j++) {
+    mark[j] = j;
+    for (int k = Qfp[j]; k < Qfp[j + 1]; k++) { const int i = Qfi[k]; if (mark[i] != j) { mark[i] = j; adji.push_back(i); } }
+    for (int p = Ap[j]; p < Ap[j + 1]; p++) adji.push_back(n + Ai[p]);
+    adjp[j + 1] = (int)adji.size();
+  }
+  for (int k = 0; k < m; k++) {
+    for (int q = Atp[k]; q < Atp[k + 1]; q++) adji.push_back(Ati[q]);
+    adjp[n + k + 1] = (int)adji.size();
+  }
+}
+static void sparse_order(const SparseAdj &G, const int n, std::vector<int> &perm) {
+  const std::vector<int> &adjp = G.p, &adji = G.i;
+  const int LEAF = 24;
   const size_t hub_deg = std::max<size_t>(48, 10 * (adji.size() / std::max(n, 1) + 1));
   std::vector<int> part((size_t)n, 0), level((size_t)n, 0), queue((size_t)n);
   perm.assign((size_t)n, -1);
@@ -719,11 +755,9 @@ static void sparse_order(const qpg_batch *bt, size_t b, std::vector<int> &perm) 
     stack.push_back(Item{std::move(Bn), it.lo + na});
   }
 }
-static int sparse_analyze(const qpg_batch *bt, size_t b, SparseSym &S, size_t max_nnz, std::string &why) {
-  const HostProblem &P = bt->probs[b];
-  const int n = P.n;
-  const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
-  const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
+/* cols(jo, visit) calls visit(i) for the row indices i (original numbering; repeats allowed) of column jo of the matrix to factorise */
+template <class Cols>
+static int sparse_analyze(const int n, const Cols &cols, SparseSym &S, size_t max_nnz, std::string &why) {
   if (S.perm.size() != (size_t)n) { S.perm.resize((size_t)n); for (int j = 0; j < n; j++) S.perm[j] = j; }
   S.iperm.assign((size_t)n, 0);
   for (int j = 0; j < n; j++) S.iperm[S.perm[j]] = j;
@@ -734,12 +768,7 @@ static int sparse_analyze(const qpg_batch *bt, size_t b, SparseSym &S, size_t ma
   for (int j = 0; j < n; j++) { /* column j of P H P' = column perm[j] of H, rows renumbered */
     col.clear();
     mark[j] = j;
-    const int jo = perm[j];
-    for (int k = Qfp[jo]; k < Qfp[jo + 1]; k++) { const int i = ip[Qfi[k]]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } }
-    for (int p = Ap[jo]; p < Ap[jo + 1]; p++) {
-      const int t = Ai[p];
-      for (int q = Atp[t]; q < Atp[t + 1]; q++) { const int i = ip[Ati[q]]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } }
-    }
+    cols(perm[j], [&](const int io) { const int i = ip[io]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } });
     for (int c = child_head[j]; c >= 0; c = child_next[c])
       for (int e = S.Lp[c]; e < S.Lp[c + 1]; e++) { const int i = S.Li[e]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } }
     std::sort(col.begin(), col.end());
@@ -777,21 +806,40 @@ static int sparse_analyze(const qpg_batch *bt, size_t b, SparseSym &S, size_t ma
  * all slots, upload */
 static int sparse_setup(qpg_batch *bt) {
   qpg_view &V = bt->V;
-  const size_t B = bt->B, n = bt->n, ns = bt->nslots;
+  const size_t B = bt->B, n = bt->nfac, ns = bt->nslots; /* n: rows of the factor (n + m in KKT mode) */
   std::vector<SparseSym> sym(B);
   std::vector<int> rc(B, 0);
   std::vector<std::string> why(B);
   const size_t max_nnz = (size_t)1 << 30; /* int32 positions; 8 GB of values per slot */
   const int ordering = bt->ctx->sparse_ordering;
+  const bool kkt = bt->kkt != 0;
   parallel_for(B, [&](size_t b) {
     sym[b].dissected = false;
-    if (ordering != 1) rc[b] = sparse_analyze(bt, b, sym[b], max_nnz, why[b]); /* natural ordering */
-    const bool deep = ordering == 1 || (ordering < 0 && rc[b] == 0 && sym[b].nlev > 256 && (size_t)sym[b].nlev * 8 > (size_t)bt->probs[b].n);
+    const HostProblem &P = bt->probs[b];
+    if (kkt) {
+      /* K_full: nested dissection unless the natural order [x; y] is asked for (under [x; y] a banded Q fills the whole constraint block:
+       * about n m entries); the dense rows of A are high-degree vertices, set aside and ordered last */
+      SparseAdj G;
+      sparse_adj_K(bt, b, G);
+      const int nf = P.n + P.m;
+      if (ordering != 0) { sparse_order(G, nf, sym[b].perm); sym[b].dissected = true; }
+      auto cols = [&G](const int jo, auto &&visit) { for (int e = G.p[jo]; e < G.p[jo + 1]; e++) visit(G.i[e]); };
+      rc[b] = sparse_analyze(nf, cols, sym[b], max_nnz, why[b]);
+      return;
+    }
+    const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
+    const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
+    auto cols = [=](const int jo, auto &&visit) { /* H = Q + A'A with ALL rows of A */
+      for (int k = Qfp[jo]; k < Qfp[jo + 1]; k++) visit(Qfi[k]);
+      for (int p = Ap[jo]; p < Ap[jo + 1]; p++) { const int t = Ai[p]; for (int q = Atp[t]; q < Atp[t + 1]; q++) visit(Ati[q]); }
+    };
+    if (ordering != 1) rc[b] = sparse_analyze(P.n, cols, sym[b], max_nnz, why[b]); /* natural ordering */
+    const bool deep = ordering == 1 || (ordering < 0 && rc[b] == 0 && sym[b].nlev > 256 && (size_t)sym[b].nlev * 8 > (size_t)P.n);
     if (!deep) return;
     SparseSym nd;
-    sparse_order(bt, b, nd.perm);
+    { SparseAdj G; sparse_adj_H(bt, b, G); sparse_order(G, P.n, nd.perm); }
     std::string why_nd;
-    const int rc_nd = sparse_analyze(bt, b, nd, max_nnz, why_nd);
+    const int rc_nd = sparse_analyze(P.n, cols, nd, max_nnz, why_nd);
     nd.dissected = true;
     /* automatic: kept when the tree is at least four times shallower and the factor at most three times larger */
     if (ordering == 1) { rc[b] = rc_nd; why[b] = why_nd; sym[b] = std::move(nd); }
@@ -841,7 +889,7 @@ static int sparse_setup(qpg_batch *bt) {
       for (int t = 0; t < P.m; t++) {
         int f = P.n;
         for (int q = Atp[t]; q < Atp[t + 1]; q++) { atip[(size_t)q] = ip[Ati[q]]; f = std::min(f, ip[Ati[q]]); }
-        first[(size_t)t] = f;
+        first[(size_t)t] = kkt ? ip[P.n + t] : f; /* KKT mode: the constraint's own row / column of K in the factor's numbering */
       }
       for (int k = 0; k < P.nzQf; k++) qfip[(size_t)k] = ip[Qfi[k]];
       RT_MEMCPY_H2D(V.sp_perm + b * n, bt->sp_perm.data() + b * n, n * 4);
@@ -873,13 +921,14 @@ extern "C" int qpg_batch_sparse_info(qpg_batch *bt, qpg_int idx, qpg_int *nnzL, 
 }
 
 /* the ordering of one member's sparse factor: P H P' = L D L' with perm[new] = old (n entries; identity = the reference's natural
- * ordering), and the height of its elimination tree */
+ * ordering), and the height of its elimination tree; in KKT mode P K P' = L D L' (n + m entries, [x; y] numbering) */
 extern "C" int qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, qpg_int *levels) {
   if (!bt || !bt->is_setup) return fail(QPG_ERR_INVALID, "qpg_batch_sparse_perm: batch is not set up");
   if (!bt->sparse) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_sparse_perm: the batch keeps dense factors");
   if (idx < 0 || idx >= bt->B) return fail(QPG_ERR_INVALID, "qpg_batch_sparse_perm: bad index");
-  const int n = bt->probs[(size_t)idx].n;
-  if (perm) for (int j = 0; j < n; j++) perm[j] = bt->sp_perm[(size_t)idx * bt->n + j];
+  const HostProblem &P = bt->probs[(size_t)idx];
+  const int nf = bt->kkt ? P.n + P.m : P.n; /* rows of the member's factor: n + m in KKT mode */
+  if (perm) for (int j = 0; j < nf; j++) perm[j] = bt->sp_perm[(size_t)idx * bt->nfac + j];
   if (levels) *levels = bt->sp_levels[(size_t)idx];
   return api_ok();
 }
@@ -1472,6 +1521,8 @@ extern "C" int qpg_batch_update_settings(qpg_batch *bt, const QPGSettings *s) { 
     return fail(QPG_ERR_UNSUPPORTED, "nonconvex is fixed at setup (set_settings_nonconvex runs in qpalm_setup, qpalm.c:293-296)");
   if (((s->factorization_method == 0) ? 1 : 0) != bt->kkt)
     return fail(QPG_ERR_UNSUPPORTED, "factorization_method is fixed at setup (qpalm_set_factorization_method runs in qpalm_setup, qpalm.c:196)");
+  if (bt->kkt && bt->sparse && s->enable_dual_termination)
+    return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_update_settings: the sparse KKT factor does not support enable_dual_termination (no LD_Q on the pattern of K)");
   const int extra = (int)(s->scaling - bt->settings.scaling);
   bt->settings = *s;
   if (ensure_dual_slots(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (LD_Q slots)");
@@ -1534,7 +1585,10 @@ static int run_op(qpg_batch *bt, qpg_int idx, int op, const char *fn) {
   if (idx < 0 || idx >= bt->B || idx >= bt->nslots) return fail(QPG_ERR_INVALID, std::string(fn) + ": bad index (needs idx < max_slots)");
   const int rpt = bt->sparse ? 1 : (bt->nfac + bt->threads - 1) / bt->threads;
   const size_t shm = (size_t)bt->lds_bytes;
-  if (bt->sparse && (op == QP_OP_LDLCHOL || op == QP_OP_LDLCHOL_QATSA || op == QP_OP_UPDATE_ENTER || op == QP_OP_DOWNDATE_LEAVE || op == QP_OP_UPDATE_SIGMA || op == QP_OP_SOLVE)) {
+  const bool sp_kkt_op = bt->kkt && (op == QP_OP_KKT_FORM || op == QP_OP_KKT_FACTOR || op == QP_OP_KKT_ENTER || op == QP_OP_KKT_LEAVE || op == QP_OP_KKT_SOLVE);
+  if (bt->sparse && bt->kkt && (op == QP_OP_LDLCHOL || op == QP_OP_LDLCHOL_QATSA || op == QP_OP_UPDATE_ENTER || op == QP_OP_DOWNDATE_LEAVE || op == QP_OP_UPDATE_SIGMA || op == QP_OP_SOLVE))
+    return fail(QPG_ERR_UNSUPPORTED, std::string(fn) + ": Schur-mode factor operation (this batch keeps a sparse L D L' of K)");
+  if (bt->sparse && (sp_kkt_op || op == QP_OP_LDLCHOL || op == QP_OP_LDLCHOL_QATSA || op == QP_OP_UPDATE_ENTER || op == QP_OP_DOWNDATE_LEAVE || op == QP_OP_UPDATE_SIGMA || op == QP_OP_SOLVE)) {
     BT_LAUNCH(bt, k_op_sparse, 1, shm, bt->V, (int)idx, op); /* the factor operations of solver_interface.h on the sparse L D L' (round 6) */
     if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, std::string(fn) + " failed: " + RT_LAST_ERROR());
     return api_ok();

@@ -344,6 +344,14 @@ QPP int dev_update_sigma_pre(const qpg_view &V, const QpArrays &a, IterShared &I
   if (V.offload && V.update_rank_threshold >= 0) thr = qmin(thr, (double)V.update_rank_threshold); /* coop mode: beyond its threshold the factor is rebuilt by many workgroups
                                                                         instead of updated by one (speed policy, same matrix) */
   int nupd = 0;
+  if (V.kkt) {
+    /* FACTORIZE_KKT (iteration.c:135-144, solver_interface.c:463-481): every branch that changes anything ends in
+     * reset_newton = TRUE; the reference's rank-1 correction is applied at row pinv[row] (a variable's row) and is
+     * overwritten by the refactorisation that reset_newton forces, so it is not restated (dense panel and sparse factor of K alike) */
+    if (I.s.kkt_first || (qp_prox(st, I.s) && I.s.gamma < qp_gamma_max(st, I.s)) || nchg > 0) { if (tid == 0) I.s.reset_newton = 1; }
+    __syncthreads();
+    return 0;
+  }
   if (V.sparse) {
     /* sparse factor (qpalm_sparse.h): ldlupdate_sigma_changed as the reference has it (solver_interface.c:443-503) -- rank-1 updates with the scaled rows along
      * their elimination-tree paths -- where walking the paths is cheaper than rebuilding (sp_update_pays, the rule of the entering / leaving rows); else the
@@ -357,14 +365,6 @@ QPP int dev_update_sigma_pre(const qpg_view &V, const QpArrays &a, IterShared &I
     }
     __syncthreads();
     return nupd;
-  }
-  if (V.kkt) {
-    /* FACTORIZE_KKT (iteration.c:135-144, solver_interface.c:463-481): every branch that changes anything ends in
-     * reset_newton = TRUE; the reference's rank-1 correction is applied at row pinv[row] (a variable's row) and is
-     * overwritten by the refactorisation that reset_newton forces, so it is not restated */
-    if (I.s.kkt_first || (qp_prox(st, I.s) && I.s.gamma < qp_gamma_max(st, I.s)) || nchg > 0) { if (tid == 0) I.s.reset_newton = 1; }
-    __syncthreads();
-    return 0;
   }
   if ((qp_prox(st, I.s) && I.s.gamma < qp_gamma_max(st, I.s)) || ((double)nchg > thr)) {
     if (tid == 0) I.s.reset_newton = 1;
@@ -679,6 +679,7 @@ QPP double dev_dual_objective(const qpg_view &V, const QpArrays &a, int b, const
 
 #include "qpalm_kkt.h"
 #include "qpalm_sparse.h"
+#include "qpalm_sparse_kkt.h"
 
 /* ... and with the sparse factor (round 6): LD_Q = the L D L' of Q alone on the pattern of the main factor (a superset of Q's own: the entries
  * outside it come out as exact zeros), in a second value array per slot; the same sums */
@@ -1031,6 +1032,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
       else if (la == 4) sp_updown(V, b, n, SP, a.enter(), n_sig, a.leave(), 0); /* ldlupdate_sigma_changed: the rows listed in enter[], scaled by dev_ldlupdate_sigma_scale */
       else if (la == 1 || la == 3) sp_factor(V, b, n, SP, la == 1, prox != 0, gam);
       else if (la == 5) gersh_ub = sp_gershgorin(V, b, n, SP, I.S);
+      else if (la == 8) spk_newton(&V, b, slot, Dg, &I, lds, action, I.s.nb_enter, I.s.nb_leave, QP_KKT_SOLVE | QP_KKT_REFINE); /* KKT mode: the sparse factor of K */
       else if (la == 7) { /* qpalm.c:459-468: LD_Q = the factor of Q alone (no A' Sigma A, no I / gamma) and the dual objective of the starting point */
         SpArrays SQ = SP; SQ.Lx = LQ; SQ.Dg = DgQ;
         sp_factor(V, b, n, SQ, false, false, gam);
@@ -1089,8 +1091,10 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
     if (kind == QP_KIND_NEWTON) {
       /* ldlsolveLD_neg_dphi (solver_interface.c:505-519) */
       if constexpr (SPARSE) {
-        for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1;
-        sp_solve(n, sp_arrays(V, b, slot, Dg, lds), a.d());
+        if (!V.kkt) { /* (KKT mode: spk_newton has solved) */
+          for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1;
+          sp_solve(n, sp_arrays(V, b, slot, Dg, lds), a.d());
+        }
       } else
       if (!V.kkt && !resume) {
         const bool fused = (RPT > 0) && !QP_NOFUSE && (action == 2) && !V.offload;

@@ -519,6 +519,12 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_op_sparse(qpg_view V, int
       __syncthreads();
       sp_solve(n, SP, a.d());
       break;
+    /* the KKT operations on the sparse factor of K (batches created with FACTORIZE_KKT under "sparse_kkt" = 1; qpalm_sparse_kkt.h) */
+    case QP_OP_KKT_FORM: if (V.kkt) spk_newton(&V, b, slot, SP.Dg, &I, QP_DYN_LDS(), 3, 0, 0, 0); break;
+    case QP_OP_KKT_FACTOR: if (V.kkt) spk_newton(&V, b, slot, SP.Dg, &I, QP_DYN_LDS(), 4, 0, 0, 0); break;
+    case QP_OP_KKT_ENTER: if (V.kkt) spk_newton(&V, b, slot, SP.Dg, &I, QP_DYN_LDS(), 2, I.s.nb_enter, 0, 0); break;
+    case QP_OP_KKT_LEAVE: if (V.kkt) spk_newton(&V, b, slot, SP.Dg, &I, QP_DYN_LDS(), 2, 0, I.s.nb_leave, 0); break;
+    case QP_OP_KKT_SOLVE: if (V.kkt) spk_newton(&V, b, slot, SP.Dg, &I, QP_DYN_LDS(), 0, 0, 0, QP_KKT_SOLVE); break;
     default: break;
   }
   __syncthreads();

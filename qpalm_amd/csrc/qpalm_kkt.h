@@ -167,6 +167,34 @@ QPD void kkt_residual(const qpg_view &V, const QpArrays &a, int b, IterShared &I
   norm_Ksol = vm[0]; norm_r = vm[1];
 }
 
+/* iterative refinement (newton.c:57-90; constants.h:101-103) of the solution in sol (and its first n entries in d): solve(v) replaces v (n + m
+ * entries, [x; y]) by K^{-1} v with the factor the slot holds -- the dense panel (kkt_newton) or the sparse L D L' (qpalm_sparse_kkt.h) */
+template <class Solve>
+QPD void kkt_refine(const qpg_view &V, const QpArrays &a, int b, IterShared &I, double gamma, int prox, double *sol, double *rhs, double *z, Solve &solve_in_place) {
+  const int n = a.n, np = a.n + a.m, tid = threadIdx.x;
+  double nK, res;
+  kkt_residual(V, a, b, I, gamma, prox, nK, res);
+  double vm[1] = {0.0}, vs[1] = {0.0};
+  for (int j = tid; j < n; j += QP_T) vm[0] = qmax(vm[0], qabs(a.dphi()[j]));
+  block_reduce<1, 0>(I.S, vm, vs);
+  const double ref_norm = qmax(nK, vm[0]);
+  int kref = 0;
+  while (kref < 3 && QP_UNIFORM((int)(res > qmax(1e-10 * ref_norm, 1e-12)))) {
+    kref++;
+    __syncthreads();
+    for (int j = tid; j < np; j += QP_T) z[j] = rhs[j]; /* the correction solve works in place on a copy */
+    __syncthreads();
+    solve_in_place(z);
+    for (int j = tid; j < np; j += QP_T) {
+      const double dz = z[j];
+      if (j < n) a.d()[j] = dz + 1 * a.d()[j];
+      sol[j] = 1 * dz + 1 * sol[j];
+    }
+    kkt_residual(V, a, b, I, gamma, prox, nK, res);
+  }
+  __syncthreads();
+}
+
 /* The KKT branch.  action: 1 (re)form + factorise (qpalm_form_kkt / qpalm_reform_kkt + ladel_factorize*), 2 row additions for
  * enter[0 .. ne) then row deletions for leave[0 .. nl) (kkt_update_entering_constraints / kkt_update_leaving_constraints),
  * 3 form only, 4 factorise what the slot holds, 5 spread a compact factor out to the full layout, 0 keep.  flags: 1 kkt_solve (solver_interface.c:238-247), 2 the iterative
@@ -291,28 +319,7 @@ QPNI void kkt_newton(const qpg_view *Vp, int b_, double *L, double *Dg, double *
   solve_in_place(sol);
   for (int j = tid; j < n; j += QP_T) a.d()[j] = sol[j];
   if (!(flags & QP_KKT_REFINE)) { __syncthreads(); return; }
-  /* iterative refinement (newton.c:57-90; constants.h:101-103) */
-  double nK, res;
-  kkt_residual(V, a, b, I, gamma, prox, nK, res);
-  double vm[1] = {0.0}, vs[1] = {0.0};
-  for (int j = tid; j < n; j += QP_T) vm[0] = qmax(vm[0], qabs(a.dphi()[j]));
-  block_reduce<1, 0>(I.S, vm, vs);
-  const double ref_norm = qmax(nK, vm[0]);
-  int kref = 0;
-  while (kref < 3 && QP_UNIFORM((int)(res > qmax(1e-10 * ref_norm, 1e-12)))) {
-    kref++;
-    __syncthreads();
-    for (int j = tid; j < np; j += QP_T) z[j] = rhs[j]; /* the correction solve works in place on a copy */
-    __syncthreads();
-    solve_in_place(z);
-    for (int j = tid; j < np; j += QP_T) {
-      const double dz = z[j];
-      if (j < n) a.d()[j] = dz + 1 * a.d()[j];
-      sol[j] = 1 * dz + 1 * sol[j];
-    }
-    kkt_residual(V, a, b, I, gamma, prox, nK, res);
-  }
-  __syncthreads();
+  kkt_refine(V, a, b, I, gamma, prox, sol, rhs, z, solve_in_place);
 }
 
 #endif

@@ -50,7 +50,8 @@
 #endif
 struct SpArrays { /* this QP's symbolic arrays + this slot's values and work vectors */
   const int *Lp, *Li, *Rp, *Rk, *Rpos, *levptr, *levcol;
-  const int *perm, *AtiP, *QfiP, *first; /* the factor's numbering (P H P'): perm[new] = old; Ati and Qfi renumbered; every row of A's first column */
+  const int *perm, *AtiP, *QfiP, *first; /* the factor's numbering (P H P'): perm[new] = old; Ati and Qfi renumbered; every row of A's first column
+                                            (KKT mode, qpalm_sparse_kkt.h: every constraint's own row / column of P K P') */
   int nlev;
   double *Lx, *Dg, *wv, *tmp;
   char *lds;     /* the workgroup's dynamic LDS (nothing else lives there while a factor operation runs) */
@@ -59,12 +60,13 @@ struct SpArrays { /* this QP's symbolic arrays + this slot's values and work vec
 QPD SpArrays sp_arrays(const qpg_view &V, int b, int slot, double *Dg, char *lds) {
   SpArrays s;
   s.lds = lds; s.lds_bytes = V.lds_bytes; s.lds_cap = V.sp_lds;
-  s.Lp = V.sp_Lp + (size_t)b * (V.n + 1); s.Li = V.sp_Li + (size_t)b * V.sp_nnzL;
-  s.Rp = V.sp_Rp + (size_t)b * (V.n + 1); s.Rk = V.sp_Rk + (size_t)b * V.sp_nnzL; s.Rpos = V.sp_Rpos + (size_t)b * V.sp_nnzL;
-  s.levptr = V.sp_levptr + (size_t)b * (V.n + 1); s.levcol = V.sp_levcol + (size_t)b * V.n;
-  s.perm = V.sp_perm + (size_t)b * V.n; s.AtiP = V.sp_AtiP + (size_t)b * V.nnzA; s.QfiP = V.sp_QfiP + (size_t)b * V.nnzQf; s.first = V.sp_first + (size_t)b * V.m;
+  const size_t nf = V.nfac; /* rows of the factor: n, or n + m in KKT mode */
+  s.Lp = V.sp_Lp + (size_t)b * (nf + 1); s.Li = V.sp_Li + (size_t)b * V.sp_nnzL;
+  s.Rp = V.sp_Rp + (size_t)b * (nf + 1); s.Rk = V.sp_Rk + (size_t)b * V.sp_nnzL; s.Rpos = V.sp_Rpos + (size_t)b * V.sp_nnzL;
+  s.levptr = V.sp_levptr + (size_t)b * (nf + 1); s.levcol = V.sp_levcol + (size_t)b * nf;
+  s.perm = V.sp_perm + (size_t)b * nf; s.AtiP = V.sp_AtiP + (size_t)b * V.nnzA; s.QfiP = V.sp_QfiP + (size_t)b * V.nnzQf; s.first = V.sp_first + (size_t)b * V.m;
   s.nlev = V.sp_nlev[b];
-  s.Lx = V.sp_Lx + (size_t)slot * V.sp_nnzL; s.Dg = Dg; s.wv = V.sp_wv + (size_t)slot * QP_NW * V.sp_gpw * V.n; s.tmp = V.sp_tmp + (size_t)slot * V.n;
+  s.Lx = V.sp_Lx + (size_t)slot * V.sp_nnzL; s.Dg = Dg; s.wv = V.sp_wv + (size_t)slot * QP_NW * V.sp_gpw * nf; s.tmp = V.sp_tmp + (size_t)slot * nf;
   return s;
 }
 
@@ -74,8 +76,12 @@ QPD bool sp_level_needs_barrier(const SpArrays &S, int lev) {
   return (S.levptr[lev + 1] - S.levptr[lev] > 1) || (S.levptr[lev + 2] - S.levptr[lev + 1] > 1);
 }
 /* H = Q (+ A' Sigma_act A) (+ I / gamma) assembled column by column and factorised in the same pass (see the header).
- * with_AtSA = false, proximal = false: the second resident factor LD_Q of the dual objective (dev_solve, la == 7), into the value arrays the caller points S at. */
-QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma) {
+ * with_AtSA = false, proximal = false: the second resident factor LD_Q of the dual objective (dev_solve, la == 7), into the value arrays the caller points S at.
+ * KKT = true (qpalm_sparse_kkt.h; with_AtSA = false): K = [[Q + I / gamma, A_a'], [A_a, -Sigma_a^-1]] of n = nv + m rows instead -- a variable's column
+ * (perm[j] < nv) takes Q, 1 / gamma and A's entries toward the constraints with kkt_state 1; such a constraint's column (non-empty: a constraint
+ * with an entry) its row of A and -1 / sigma; any other constraint's column a unit diagonal.  The updates and the pivots are the same code. */
+template <bool KKT = false>
+QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma, int nv = 0) {
   /* a column per GROUP of lanes: the columns of a sparse factor are short (a band: half a dozen entries), so a wavefront takes gpw = 1, 2,
    * 4 or 8 columns of the level at a time (8 lanes each at 8) and a 512-thread workgroup up to 64 -- every step of a column is a chain of
    * dependent HBM round trips, the groups' chains overlap.  Loops run to the wavefront's longest trip count with the other groups
@@ -89,6 +95,8 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
   const int *Qfp = V.Qfp + (size_t)b * (V.n + 1);
   const double *Qfx = V.Qfx + (size_t)b * V.nnzQf;
   const int *active = V.active + (size_t)b * V.m;
+  const int *kstate = V.kkt_state + (size_t)b * V.m; /* (KKT) */
+  const double *Ax = V.Ax + (size_t)b * V.nnzA, *Atx = V.Atx + (size_t)b * V.nnzA, *sigma_inv = V.sigma_inv + (size_t)b * V.m;
 #if QP_SP_LOCAL
   const SpArrays S = S_; /* (a real function: the fields of S_ would be re-read from the caller's frame after every store) */
   const int *Li = QP_UNIFORM_PTR(S.Li), *Lp = QP_UNIFORM_PTR(S.Lp), *Rp = QP_UNIFORM_PTR(S.Rp), *Rk = QP_UNIFORM_PTR(S.Rk), *Rpos = QP_UNIFORM_PTR(S.Rpos);
@@ -124,7 +132,25 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
       const bool on = c < c1;
       const int j = on ? S.levcol[c] : 0;
       const int jo = on ? S.perm[j] : 0; /* column j of P H P' is column perm[j] of H; row indices through AtiP / QfiP */
+      const bool qcol = on && (!KKT || jo < nv); /* a column with Q's entries (KKT: a variable's) */
       const int e0 = on ? S.Lp[j] : 0, e1 = on ? S.Lp[j + 1] : 0;
+      /* K's coupling entries of column j (after Q, before 1 / gamma): lanes over the entries -- distinct rows -- then the constraint's diagonal */
+      auto kkt_coupling = [&](auto acc, auto diag) QP_ALWAYS_INLINE {
+        const bool isc = on && !qcol;
+        const int k = isc ? jo - nv : 0;
+        const int q0 = qcol ? Ap[jo] : (isc ? Atp[k] : 0), q1 = qcol ? Ap[jo + 1] : (isc ? Atp[k + 1] : 0);
+        const bool present = isc && kstate[k] == 1 && q1 > q0;
+        for (int q = q0 + gl; q < q1; q += spg) {
+          int i = -1;
+          double v = 0.0;
+          if (qcol) { const int t = Ai[q]; if (kstate[t] == 1) { i = S.first[t]; v = Ax[q]; } }
+          else if (present) { i = AtiP[q]; v = Atx[q]; }
+          if (i >= j) acc(i, v);
+        }
+        QP_WAVE_SYNC();
+        if (isc && gl == 0) diag(present ? -sigma_inv[k] : 1.0);
+        QP_WAVE_SYNC();
+      };
       if (cap > 0 && wave_imax(e1 - e0 + 1) <= cap) {
         const int len = e1 - e0;
         auto posof = [&](const int i) QP_ALWAYS_INLINE { /* position of row i (>= j, in the pattern) among the accumulators */
@@ -138,7 +164,7 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
          * of L), so that the column pays ~7 dependent round trips instead of one or two per contributing row / column ---- */
         const bool wA = on && with_AtSA;
         const int p0 = wA ? Ap[jo] : 0, p1 = wA ? Ap[jo + 1] : 0;
-        const int k0 = on ? Qfp[jo] : 0, k1 = on ? Qfp[jo + 1] : 0;
+        const int k0 = qcol ? Qfp[jo] : 0, k1 = qcol ? Qfp[jo + 1] : 0;
         const int r0 = on ? Rp[j] : 0, r1 = on ? Rp[j + 1] : 0;
         const int f_li = (e0 + gl < e1) ? Li[e0 + gl] : 0;
         int f_t = -1, f_ainv = 0, f_qi = -1, f_k = -1, f_tpos = 0;
@@ -253,7 +279,8 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
           if (i >= j) { const int p = posof(i); wl[p] = Qfx[k] + wl[p]; }
         }
         QP_WAVE_SYNC();
-        if (on && proximal && gl == 0) wl[0] += 1.0 / gamma;
+        if constexpr (KKT) kkt_coupling([&](int i, double v) QP_ALWAYS_INLINE { const int p = posof(i); wl[p] += v; }, [&](double v) QP_ALWAYS_INLINE { wl[0] = v; });
+        if (qcol && proximal && gl == 0) wl[0] += 1.0 / gamma;
         QP_WAVE_SYNC();
         /* ---- left-looking updates: every column k < j with l_jk != 0, ascending ---- */
         for (int rb = 0; rb < nr; rb += spg) {
@@ -311,14 +338,15 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
       }
       /* ---- + Q(:, j) (both triangles are stored: the lower one of the permuted matrix is picked here), + 1 / gamma ---- */
       {
-        const int k0 = on ? Qfp[jo] : 0, k1 = on ? Qfp[jo + 1] : 0;
+        const int k0 = qcol ? Qfp[jo] : 0, k1 = qcol ? Qfp[jo + 1] : 0;
         for (int k = k0 + gl; k < k1; k += spg) {
           const int i = S.QfiP[k];
           if (i >= j) w[i] = Qfx[k] + w[i];
         }
       }
       QP_WAVE_SYNC();
-      if (on && proximal && gl == 0) w[j] += 1.0 / gamma;
+      if constexpr (KKT) kkt_coupling([&](int i, double v) QP_ALWAYS_INLINE { w[i] += v; }, [&](double v) QP_ALWAYS_INLINE { w[j] = v; });
+      if (qcol && proximal && gl == 0) w[j] += 1.0 / gamma;
       QP_WAVE_SYNC();
       /* ---- left-looking updates: every column k < j with l_jk != 0, ascending.  Column k was finished in an earlier level, so l_jk, d_k
        * and the column's extent can be fetched for spg of them at once (one lane each), then applied in order ---- */
@@ -412,6 +440,35 @@ QPN double sp_gershgorin(const qpg_view &V, int b, const int n, const SpArrays &
  * w_i <- w_i - w_j l_ij, l_ij <- l_ij - gamma w_i.  Columns off the path are not touched.  Cost: one chain step (a few dependent HBM
  * round trips) per path column -- cheap on bushy trees (block structure), hopeless on a chain (band matrix): sp_update_pays decides. */
 /* (sp_update_pays: qpalm_iter.h, in front of dev_update_sigma_pre, which applies the same rule to changed penalties) */
+/* ONE rank-1 update (update) or downdate of the factor with the vector in w (dense, zero off the path; consumed), walked from column j to the root;
+ * wavefront 0 alone.  Row additions / deletions of the KKT factor (qpalm_sparse_kkt.h) start it at the parent of the row's column */
+template <class W>
+QPD void sp_path_walk(const int *Lp, const int *Li, double *Lx, double *Dg, W w, int j, const bool update) {
+  const int lane = threadIdx.x & 63;
+  double alpha = 1.0;
+  while (j >= 0) {
+    const int e0 = Lp[j], e1 = Lp[j + 1];
+    const double wj = w[j];
+    double dj = Dg[j], a, gam;
+    QP_WAVE_SYNC(); /* every lane has read w_j and d_j before lane 0 overwrites them below */
+    if (update) { a = alpha + (wj * wj) / dj; dj *= a; gam = -wj / dj; }
+    else        { a = alpha - (wj * wj) / dj; dj *= a; gam =  wj / dj; }
+    dj /= alpha;
+    alpha = a;
+    int ifirst = -1; /* lane 0: the first row of the column's pattern = the parent = the next column of the path */
+    for (int e = e0 + lane; e < e1; e += 64) {
+      const int i = Li[e];
+      const double lx = Lx[e];
+      const double wi = w[i] - wj * lx;
+      w[i] = wi;
+      Lx[e] = lx - gam * wi;
+      if (e == e0) ifirst = i;
+    }
+    if (lane == 0) { Dg[j] = dj; w[j] = 0.0; }
+    QP_WAVE_SYNC();
+    j = __shfl(ifirst, 0);
+  }
+}
 QPNI void sp_updown(const qpg_view &V, int b, const int n, const SpArrays &S_, const int *up, int n_up, const int *dn, int n_dn) {
 #if QP_SP_LOCAL
   const SpArrays S = S_;
@@ -434,30 +491,7 @@ QPNI void sp_updown(const qpg_view &V, int b, const int n, const SpArrays &S_, c
       if (q1 <= q0) continue;
       for (int q = q0 + lane; q < q1; q += 64) w[AtiP[q]] = Atss[q];
       QP_WAVE_SYNC();
-      double alpha = 1.0;
-      int j = S.first[t]; /* the row's first column in the factor's numbering: the path starts there */
-      while (j >= 0) {
-        const int e0 = Lp[j], e1 = Lp[j + 1];
-        const double wj = w[j];
-        double dj = Dg[j], a, gam;
-        QP_WAVE_SYNC(); /* every lane has read w_j and d_j before lane 0 overwrites them below */
-        if (update) { a = alpha + (wj * wj) / dj; dj *= a; gam = -wj / dj; }
-        else        { a = alpha - (wj * wj) / dj; dj *= a; gam =  wj / dj; }
-        dj /= alpha;
-        alpha = a;
-        int ifirst = -1; /* lane 0: the first row of the column's pattern = the parent = the next column of the path */
-        for (int e = e0 + lane; e < e1; e += 64) {
-          const int i = Li[e];
-          const double lx = Lx[e];
-          const double wi = w[i] - wj * lx;
-          w[i] = wi;
-          Lx[e] = lx - gam * wi;
-          if (e == e0) ifirst = i;
-        }
-        if (lane == 0) { Dg[j] = dj; w[j] = 0.0; }
-        QP_WAVE_SYNC();
-        j = __shfl(ifirst, 0);
-      }
+      sp_path_walk(Lp, Li, Lx, Dg, w, S.first[t], update); /* the row's first column in the factor's numbering: the path starts there */
     }
   };
   __syncthreads();

@@ -118,15 +118,21 @@ def config5_qp(n=5000, m=5000, seed=55):
     return QP(n, m, Q.indptr.astype(np.int64), Q.indices.astype(np.int64), Q.data.copy(), p.Ap, p.Ai, p.Ax, p.q, p.bmin, p.bmax)
 
 
-def sparse_qp(n, kind="banded", seed=0, band=3, block=8, rows_per_block=4):
+def sparse_qp(n, kind="banded", seed=0, band=3, block=8, rows_per_block=4, dense_rows=1):
     """Large SPARSE convex QPs whose Schur complement Q + A'A stays sparse under the natural ordering (round 5: the sparse factor).
       banded:  Q tridiagonal-dominant with `band` sub-diagonals, A = two-variable difference rows x_i - x_{i+1} in [-1, 1] plus box rows
                on every third variable (the elimination tree is a chain: n levels);
       blocks:  block-diagonal Q with dense `block` x `block` blocks, `rows_per_block` constraints inside each block (a forest of
                n / block small trees: `block` levels, thousands of columns per level);
-      arrow:   banded, plus one dense last row / column of Q (every column of L gets one more entry)."""
+      arrow:   banded, plus one dense last row / column of Q (every column of L gets one more entry);
+      <kind>+budget (banded+budget, blocks+budget, arrow+budget):  the same QP plus `dense_rows` rows of A over ALL variables -- a budget
+               row  -1 <= sum x <= 1, then rows of random weights with the same bounds.  One such row makes Q + A'A dense; the KKT matrix
+               stays sparse with the dense rows ordered last (the sparse factor of K, context option "sparse_kkt")."""
     rng = np.random.Generator(np.random.PCG64(seed))
     rows, cols, vals = [], [], []
+    kind, _, extra = kind.partition("+")
+    if extra not in ("", "budget"):
+        raise ValueError(extra)
     if kind in ("banded", "arrow"):
         for k in range(1, band + 1):
             v = 0.3 * rng.standard_normal(n - k) / k
@@ -165,6 +171,10 @@ def sparse_qp(n, kind="banded", seed=0, band=3, block=8, rows_per_block=4):
         bmin, bmax = -rng.random(m), rng.random(m)
     else:
         raise ValueError(kind)
+    if extra == "budget":
+        D = np.vstack([np.ones(n)] + [rng.standard_normal(n) for _ in range(dense_rows - 1)])
+        A = sp.vstack([A, sp.csc_matrix(D)]).tocsc()
+        bmin, bmax = np.concatenate([bmin, -np.ones(dense_rows)]), np.concatenate([bmax, np.ones(dense_rows)])
     A.sum_duplicates(); A.sort_indices()
     Ql = sp.tril(Qf).tocsc(); Ql.sort_indices()
     q = rng.standard_normal(n)

@@ -158,9 +158,10 @@ class QpalmBatch:
         return int(z.value), int(d.value)
 
     def sparse_perm(self, b=0):
-        """(perm, levels): the ordering of member b's sparse factor (perm[new] = old; identity = natural) and the height of its elimination tree"""
-        n = self.dims[b][0]
-        perm = np.zeros(n, dtype=np.int64)
+        """(perm, levels): the ordering of member b's sparse factor (perm[new] = old; identity = natural) and the height of its elimination tree.
+        The factor has n rows, n + m in KKT mode (factorization_method = 0: P K P' with K in the [x; y] numbering)"""
+        n, m = self.dims[b]
+        perm = np.zeros(n + m if int(self.settings.factorization_method) == 0 else n, dtype=np.int64)
         lev = capi.c_int(0)
         self._check(self.L.qpg_batch_sparse_perm(self.h, int(b), perm.ctypes.data_as(C.POINTER(capi.c_int)), C.byref(lev)))
         return perm, int(lev.value)
