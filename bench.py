@@ -15,9 +15,16 @@ over RCCL inside the timed region.
 GPU, started BEFORE this process imports torch or touches HIP); under torchrun the environment is used as is.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_solve): algorithmic bytes of SURVEY.md
-section 8d, counted from device-side work counters, divided by the kernel's HIP-event duration; fractions are quoted
-against the 8 TB/s spec and against a copy kernel measured in the same run.  `cpu_baseline` times the CPU oracle
-("port") on a bounded sample of the same QPs.
+section 8d, counted from device-side work counters of the timed steps, divided by the kernel's HIP-event duration;
+the fraction is quoted against the 8 TB/s spec.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, the validity check of what the
+last step returned (every QP solved, KKT residuals of a few of them), --dump-outputs, the line.  `--full` adds every
+figure that takes a run of its own, after the line's own figures are taken: the copy and read kernels the roofline is
+also quoted against, the stand-alone LDL' solve kernel (`ldl_solve`), the PMC traffic of the same build
+(`roofline.traffic`), the two short mpc-160 sequences (`mpc160`) and `cpu_baseline`, the CPU oracle ("port") timed on
+a bounded sample of the same QPs.  In a plain run those keys are null or absent.  `outside_steps_s` says where the
+host time outside warm-up and timed steps went.
 """
 import argparse
 import json
@@ -31,6 +38,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+T_START = time.perf_counter()   # outside_steps_s counts from here (the interpreter's own start is not in it)
 
 
 def lib_sha256(path=None):
@@ -102,8 +110,11 @@ def parse_args(argv=None):
     ap.add_argument("--n", type=int, default=0, help="random workload: number of variables (default 1000)")
     ap.add_argument("--m", type=int, default=0, help="random workload: number of constraints (default 2 n)")
     ap.add_argument("--rank-threshold", type=int, default=int(os.environ.get("QPALM_RANK_THRESHOLD", "-1")))
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-mpc", action="store_true", help="skip the short mpc-160 lines (BASELINE.json config 3) appended to the default run's JSON")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in a run of its own after the timed steps: the copy / read ceilings and the "
+                         "stand-alone LDL' solve kernel, the PMC traffic lookup, the mpc-160 lines and the CPU baseline (about a minute more)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-mpc", action="store_true", help="with --full: skip the short mpc-160 lines (BASELINE.json config 3) appended to the default run's JSON")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (nccl = RCCL) and run the gather of x, y and the info records even with ONE rank: "
                          "executes the multi-GPU path's RCCL initialisation and device-view gather on a single-GPU box (tests/test_bench_launcher.py)")
@@ -495,7 +506,7 @@ def sparse_workload(args, ctx, rank, world, dist, torch):
                            "ms_per_qp_in_kernel": {"total": mean(lambda s: s.ms_total), "factor": mean(lambda s: s.ms_factor), "update": mean(lambda s: s.ms_update), "solve": mean(lambda s: s.ms_solve),
                                                    "linesearch": mean(lambda s: s.ms_linesearch), "residuals": mean(lambda s: s.ms_dbg[12])},
                            "note": "latency-bound (chains of dependent round trips per column and per level), no byte model: roofline is null for this workload"}}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(distinct, settings_kw, args.workload, budget_s=15.0, sparse=True)
         except Exception as e:   # noqa: BLE001
@@ -507,6 +518,8 @@ def sparse_workload(args, ctx, rank, world, dist, torch):
 
 # ---------------------------------------------------------------------------------------------------------------
 def worker(args):
+    marks = [("start", T_START)]           # host time outside the steps, by stage (outside_steps_s of the line)
+    mark = lambda name: marks.append((name, time.perf_counter()))
     import numpy as np
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -556,6 +569,7 @@ def worker(args):
         name, _, val = kv.partition("=")
         ctx.set_option(name, int(val))
     B = args.batch
+    mark("imports_and_device")
     if args.workload.startswith("sparse-"):
         return sparse_workload(args, ctx, rank, world, dist, torch)
     settings_kw = dict(eps_abs=1e-6, eps_rel=1e-6, verbose=0)
@@ -575,6 +589,7 @@ def worker(args):
         n, m = probs[0].n, probs[0].m
         wl = "mpc-160: batch of %d MPC QPs per GPU (T=10, nx=10, nu=5: n=%d m=%d nnz(A)=%d), eps 1e-6, scaling 10; every step moves " \
              "the initial states (update_bounds) and warm-starts from the previous solution" % (B, n, m, int(probs[0].Ap[-1]))
+    mark("problems")
     bt = QpalmBatch(ctx, probs, ctx.default_settings(**settings_kw))   # upload + Ruiz scaling: not timed
     # the arrays that cross PCIe every step of the MPC loop live in page-locked host memory (qpg_host_alloc)
     bmin_all, bmax_all = ctx.pinned_array((B, m)), ctx.pinned_array((B, m))
@@ -618,6 +633,7 @@ def worker(args):
             dist.barrier()
         torch.cuda.synchronize()
 
+    mark("batch_setup")
     for _ in range(args.warmup):
         step()
     barrier()
@@ -632,6 +648,7 @@ def worker(args):
         t = torch.tensor([elapsed], device="cuda:%d" % local, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    mark("warmup_and_steps")
 
     # ---- checks + accounting of the last step (outside the timed region) ------------------------------------
     infos, stats = bt.infos(), bt.stats_all()
@@ -678,16 +695,18 @@ def worker(args):
     phases["factor"]["TFLOPs"] = phases["factor"]["flop"] / (max(phase_ms["factor"], 1e-9) * 1e-3 * B / conc) / 1e12
     rc = 0
     if rank == 0:
-        copy_gbs = ctx.hbm_copy_gbs(1 << 30, 5)             # attainable ceilings on this box: copy (read + write) ...
-        read_gbs = ctx.hbm_read_gbs(1 << 30, 5)             # ... and a read-only stream
+        # --full: the ceilings the device attains in this run, a copy (read + write) and a read-only stream, and the stand-alone LDL' solve
+        # kernel ("HBM GB/s on LDL"); each launches kernels of its own, so a plain run leaves them (and the figures quoted against them) null
+        copy_gbs = ctx.hbm_copy_gbs(1 << 30, 5) if args.full else None
+        read_gbs = ctx.hbm_read_gbs(1 << 30, 5) if args.full else None
         model0 = byte_model(n, m, int(probs[0].Ap[-1]), int(probs[0].Qp[-1]), (n + m) if args.kkt else None)
         nsl = conc
-        ms_ldl = bt.ldlsolve_all(reps=4)                    # stand-alone LDL' solve kernel ("HBM GB/s on LDL")
+        ms_ldl = bt.ldlsolve_all(reps=4) if args.full else None
         ldl_bytes = nsl * model0["b_solve"]
         # the PMC summary of the SAME build (tools/evidence/round_artifacts.sh writes it, separate rocprofv3 --pmc passes): --traffic-json names
         # one; without the flag the committed summaries under profiles/ are tried, newest round first.  Quoted only when the hashes of the
-        # kernel sources and of the loaded library recorded in the summary equal this run's (else roofline.traffic stays null).
-        traffic, traffic_src = pmc_traffic("k_solve_pmc_traffic.json", (B, n, m), args.lib, args.traffic_json) if world == 1 else (None, None)
+        # kernel sources and of the loaded library recorded in the summary equal this run's (else roofline.traffic stays null).  --full only.
+        traffic, traffic_src = pmc_traffic("k_solve_pmc_traffic.json", (B, n, m), args.lib, args.traffic_json) if world == 1 and args.full else (None, None)
         out = {
             "metric": "QP solves/sec (batched %s); `value` = solve only, batch resident in HBM -- with qpalm_setup in the clock as the reference's run_time has it: `value_setup_plus_solve`"
                       % ("random n=%d,m=%d" % (n, m) if args.workload == "random-1000" else "MPC n=%d,m=%d, warm-started sequence" % (n, m)),
@@ -715,15 +734,15 @@ def worker(args):
                          "frac_survey_model": model_bytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                          "traffic_over_algorithmic": (traffic / tot_bytes) if traffic else None,
                          "guide_copy_GBps": 6290.0,   # MI355X_MICROARCH.md: float4 copy, 79 % of the 8 TB/s spec figure
-                         "measured_copy_GBps": copy_gbs, "measured_read_GBps": read_gbs, "frac_of_measured_copy": achieved / copy_gbs,
+                         "measured_copy_GBps": copy_gbs, "measured_read_GBps": read_gbs, "frac_of_measured_copy": (achieved / copy_gbs) if copy_gbs else None,
                          # the HBM bytes the launch really moved (PMC) per second, against the same yardsticks: how far the
                          # kernel is from the bandwidth this chip delivers to a plain copy
                          "traffic_GBps": (traffic / (kms * 1e-3) / 1e9) if traffic else None,
-                         "traffic_frac_of_measured_copy": (traffic / (kms * 1e-3) / 1e9 / copy_gbs) if traffic else None,
+                         "traffic_frac_of_measured_copy": (traffic / (kms * 1e-3) / 1e9 / copy_gbs) if traffic and copy_gbs else None,
                          "bytes_note": "update bytes = 16 B x entries of L[:, J0:] actually swept (device counter), not the 8d upper bound; solve bytes = "
                                        "8d's two passes over L minus the forward passes fused into a sweep (device counter n_fused_solve)",
                          "phases": phases},
-            "ldl_solve": {"kernel": "k_ldlsolve_all", "qps": nsl, "ms": ms_ldl, "bytes": ldl_bytes,
+            "ldl_solve": None if ms_ldl is None else {"kernel": "k_ldlsolve_all", "qps": nsl, "ms": ms_ldl, "bytes": ldl_bytes,
                           "achieved": ldl_bytes / (ms_ldl * 1e-3) / 1e9, "unit": "GB/s",
                           "frac": ldl_bytes / (ms_ldl * 1e-3) / 1e9 / HBM_PEAK_GBS,
                           "frac_of_measured_read": ldl_bytes / (ms_ldl * 1e-3) / 1e9 / read_gbs},
@@ -737,17 +756,19 @@ def worker(args):
                                             "newton_steps_redone": int(sum(int(s.n_guard_refactor) for s in stats))},
                             "phase_ms_per_qp": phase_ms},
         }
-        if world == 1 and args.workload == "random-1000" and not args.no_mpc and not args.kkt and not args.n and not args.lib:
+        if args.full and world == 1 and args.workload == "random-1000" and not args.no_mpc and not args.kkt and not args.n and not args.lib:
             # config 3 in the driver's record: Schur and KKT mode, a few warm-started steps each (outside the timed region of the headline)
             try:
                 tdir = os.path.dirname(os.path.abspath(args.traffic_json)) if args.traffic_json else None   # (the evidence run: the summaries sit next to the headline's)
                 out["mpc160"] = {"schur": mpc160_line(ctx, 8192, False, 5, traffic_dir=tdir), "kkt": mpc160_line(ctx, 2048, True, 3, traffic_dir=tdir)}
             except Exception as e:   # never lose the headline line over the side figures
                 out["mpc160"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(probs, settings_kw, args.workload)
         else:
             out["cpu_baseline"] = None
+        mark("after_steps")
+        out["outside_steps_s"] = {b[0]: round(b[1] - a[1], 3) for a, b in zip(marks, marks[1:]) if b[0] != "warmup_and_steps"}
         if not ok:
             sys.stderr.write("bench.py: INVALID RUN: %d QPs not solved, KKT spot check %.3e\n" % (n_bad, kkt))
             out["invalid"] = "%d QPs not solved, KKT spot check %.3e" % (n_bad, kkt)

@@ -67,6 +67,13 @@ def test_steps_must_be_positive():
         bench.parse_args(["--steps", "0"])
 
 
+def test_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+
+
 def test_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
     """--dump-outputs: float64 files within the budget; every QP when they fit, else the same seeded sample on every call"""
     import numpy as np
@@ -101,11 +108,12 @@ def test_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line(tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--batch", "64", "--n", "200", "--no-cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--batch", "64", "--n", "200", "--full", "--no-cpu",
                         "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, env=_env_without_dist())
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["solve_stats"]["all_solved"] and d["roofline"]["traffic"] is None
+    assert d["ldl_solve"]["ms"] > 0 and d["ldl_solve"]["frac_of_measured_read"] > 0 and d["cpu_baseline"] is None
     assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["measured_copy_GBps"] > 1000
     assert set(d["roofline"]["phases"]) == {"solve", "update", "factor", "spmv_vectors"}
     assert d["steps"] == 1 and d["ms_per_step"] > 0
@@ -114,6 +122,30 @@ def test_bench_single_gpu_line(tmp_path):
     x, y = np.load(tmp_path / "x.npy"), np.load(tmp_path / "y.npy")
     assert x.shape == (64, 200) and y.shape == (64, 400) and np.all(np.load(tmp_path / "info_status_val.npy") == 1)
     assert hashlib.sha256(x.tobytes() + y.tobytes()).hexdigest()[:16] == d["solve_stats"]["solution_sha256_16"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(tmp_path):
+    """without --full the line carries the headline and what the timed steps' own counters give; whatever takes a run of its own
+    (copy / read ceilings, the LDL' solve kernel, mpc-160 lines, CPU baseline) is null or absent, and the dumped arrays are the
+    ones --full dumps"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "64", "--n", "200"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, timeout=900, env=_env_without_dist())
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["unit"] == "QP/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["metric"].startswith("QP solves/sec")
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["solve_stats"]["all_solved"] and 0 < d["roofline"]["frac"] < 1
+    assert d["cpu_baseline"] is None and d["ldl_solve"] is None and "mpc160" not in d
+    assert all(d["roofline"][k] is None for k in ("measured_copy_GBps", "measured_read_GBps", "frac_of_measured_copy", "traffic"))
+    assert set(d["outside_steps_s"]) == {"imports_and_device", "problems", "batch_setup", "after_steps"}
+    r = subprocess.run(cmd + ["--full", "--no-cpu", "--dump-outputs", str(tmp_path / "full")], capture_output=True, text=True, timeout=900,
+                       env=_env_without_dist())
+    assert r.returncode == 0, r.stderr[-2000:]
+    import numpy as np
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "x.npy" in names
+    assert all(np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)) for f in names)
 
 
 @pytest.mark.gpu

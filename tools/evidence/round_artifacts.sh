@@ -31,9 +31,9 @@ python3 $REPO/tools/evidence/pmc_summary.py $OUT $REPO mpck_ > $OUT/mpc160_kkt_p
 rm -rf kt ktm ktk pmc_fetch pmc_write pmc_sq pmc_mpc_fetch pmc_mpc_write pmc_mpck_fetch pmc_mpck_write
 cd $REPO
 # the reported line: same build, same box, traffic from the passes above (bench.py checks the source and library hashes recorded in the summary)
-timeout 1200 python bench.py --traffic-json $OUT/k_solve_pmc_traffic.json > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python bench.py --full --traffic-json $OUT/k_solve_pmc_traffic.json > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 600 python bench.py --batch 512 --no-cpu --no-mpc > $OUT/bench_b512.json 2>> $OUT/bench_default.err
-timeout 600 python bench.py --workload mpc-160 --steps 5 > $OUT/bench_mpc160.json 2>> $OUT/bench_default.err
+timeout 600 python bench.py --full --workload mpc-160 --steps 5 > $OUT/bench_mpc160.json 2>> $OUT/bench_default.err
 timeout 600 python bench.py --workload mpc-160 --kkt --batch 2048 --steps 3 --no-cpu > $OUT/bench_mpc160_kkt.json 2>> $OUT/bench_default.err
 timeout 600 python bench.py --workload mpc-160 --steps 5 --small-workgroups 3 --no-cpu > $OUT/bench_mpc160_256_thread_instance.json 2>> $OUT/bench_default.err
 timeout 600 python bench.py --sweep-ranks 32 --no-cpu --no-mpc > $OUT/bench_sweep_ranks_32.json 2>> $OUT/bench_default.err
@@ -52,8 +52,8 @@ for b in 16 64 128 256; do timeout 300 python bench.py --batch $b --steps 3 --wa
 # the sparse factor at size
 timeout 600 python -m pytest tests/test_sparse_factor.py -q -m gpu -s --timeout 150 > $OUT/sparse_factor_at_size.txt 2>&1
 # batches of sparse QPs on the sparse factor (SURVEY section 8 row h), with the oracle's sparse-storage mode on the host cores beside them
-timeout 400 python bench.py --workload sparse-banded-2000 > $OUT/bench_sparse_banded_2000.json 2>> $OUT/bench_default.err
-timeout 400 python bench.py --workload sparse-blocks-2000 > $OUT/bench_sparse_blocks_2000.json 2>> $OUT/bench_default.err
+timeout 400 python bench.py --full --workload sparse-banded-2000 > $OUT/bench_sparse_banded_2000.json 2>> $OUT/bench_default.err
+timeout 400 python bench.py --full --workload sparse-blocks-2000 > $OUT/bench_sparse_blocks_2000.json 2>> $OUT/bench_default.err
 timeout 300 tools/evidence/sload_coherence_test > $OUT/sload_coherence.txt 2>&1
 timeout 200 tools/evidence/host_alloc_probe > $OUT/host_alloc_probe.txt 2>&1
 ls -la $OUT
