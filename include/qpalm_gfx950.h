@@ -224,6 +224,14 @@ int  qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, qpg_int *l
 int  qpg_batch_update_settings(qpg_batch *bt, const QPGSettings *s);
 int  qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, const qpg_float *bmax); /* [B][m] or NULL */
 int  qpg_batch_update_q(qpg_batch *bt, const qpg_float *q);                              /* [B][n] */
+/* qpalm_update_Q_A for every member: new values of Q and A on the sparsity patterns the batch was set up with.  Entry k of member b is the new value of
+ * the k-th entry its caller passed to qpg_batch_set_problem* (the caller's own order: duplicates and upper-triangle entries of Q included; positions
+ * past the member's own count are ignored).  Afterwards the batch is, bit for bit, what qpg_batch_setup would leave for the same patterns with the new
+ * values, the latest accepted raw q / bmin / bmax, the same c and the current settings -- without the host-side conversion, the symbolic analysis of the
+ * sparse factors or a new arena.  The stored solutions survive (qpg_batch_warm_start_last works next); an unfinished solve ends; every status goes back to
+ * unsolved and the counters of QPGStats restart.  QPG_ERR_INVALID before qpg_batch_setup or on a NULL array. */
+int  qpg_batch_update_Q_A(qpg_batch *bt, const qpg_float *Qx, const qpg_float *Ax);          /* host arrays [B][nnzQ_max], [B][nnzA_max] */
+int  qpg_batch_update_Q_A_device(qpg_batch *bt, const qpg_float *dQx, const qpg_float *dAx); /* the same layout, already in device memory (see qpg_batch_device_ptr) */
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -145,6 +145,8 @@ void qpalm_solve(QPALMWorkspace *work);
 void qpalm_update_settings(QPALMWorkspace *work, const QPALMSettings *settings);
 void qpalm_update_bounds(QPALMWorkspace *work, const c_float *bmin, const c_float *bmax);
 void qpalm_update_q(QPALMWorkspace *work, const c_float *q);
+/* upstream QPALM's qpalm_update_Q_A: new values of Q and A on the patterns of the set-up workspace, Qx / Ax in the order of the data's own arrays */
+void qpalm_update_Q_A(QPALMWorkspace *work, const c_float *Qx, const c_float *Ax);
 void qpalm_cleanup(QPALMWorkspace *work);
 
 /* ---- include/solver_interface.h (same names and argument meaning) --------------------------- */

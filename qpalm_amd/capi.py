@@ -97,6 +97,9 @@ def load(path=None):
     L.qpg_batch_update_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
     L.qpg_batch_update_bounds.argtypes = [C.c_void_p, pf, pf]
     L.qpg_batch_update_q.argtypes = [C.c_void_p, pf]
+    if hasattr(L, "qpg_batch_update_Q_A"):   # (absent from older builds of the library that tools/evidence/update_matrices_timing.py compares with)
+        L.qpg_batch_update_Q_A.argtypes = [C.c_void_p, pf, pf]
+        L.qpg_batch_update_Q_A_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -146,6 +149,7 @@ SYMBOLS = [
     "qpg_exact_linesearch", "qpg_batch_ldlsolve_all", "qpg_batch_sweep_probe", "qpg_kkt_form", "qpg_kkt_factorize",
     "qpg_kkt_update_entering_constraints", "qpg_kkt_update_leaving_constraints", "qpg_kkt_solve", "qpg_ldlchol_matrix", "qpg_sparse_matvec",
     "qpg_batch_begin_solve", "qpg_batch_get_info_all", "qpg_batch_get_stats_all", "qpg_ctx_hbm_copy_gbs", "qpg_ctx_hbm_read_gbs", "qpg_host_alloc", "qpg_host_free", "qpg_batch_set_problem_sized", "qpg_batch_set_problems",
+    "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device",
 ]
 
 

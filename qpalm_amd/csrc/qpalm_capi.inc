@@ -186,6 +186,15 @@ struct qpg_batch {
   std::string co_sig;
   long co_replays; /* graph launches of the last solve (QPALM_COOP_PROFILE prints it) */
   long co_sweeps;  /* persistent-sweep launches of the last solve (coop_test_kill counts them) */
+  /* qpg_batch_update_Q_A: entry k of the device's A / Q values of a member = entry map[k] of the arrays its caller passed to qpg_batch_set_problem*
+   * (take_column sorts a column's rows, Q keeps rows >= column).  An empty map = the same order (sorted columns, no upper entry of Q: the usual input).
+   * The maps go to the device at the first update that needs one (val_maps_d: [B][nnzA] + [B][nnzQ] positions + [B][2] "same order" flags). */
+  int nnzA_in, nnzQ_in; /* nnzA_max / nnzQ_max as the caller gave them: the strides of the arrays qpg_batch_update_Q_A takes */
+  std::vector<std::vector<int> > map_A, map_Q;
+  void *val_maps_d = nullptr; bool val_maps_current = false;
+  /* the latest accepted raw q / bmin / bmax ([B][n], [B][m] x 2): created by the first qpg_batch_update_q / _bounds after a setup as a copy of the slab's
+   * arrays + the update (the device holds them scaled in place; the slab keeps the problem as set, which a second qpg_batch_setup returns to) */
+  std::vector<double> raw_q, raw_bmin, raw_bmax;
 };
 static void co_graphs_clear(qpg_batch *bt) {
   for (auto &g : bt->co_graphs) if (g.second.ready) RT_GRAPH_FREE(g.second.exec);
@@ -289,6 +298,8 @@ extern "C" int qpg_batch_create(qpg_ctx *ctx, qpg_int B, qpg_int n, qpg_int m, q
   qpg_batch *bt = new qpg_batch();
   bt->ctx = ctx; bt->B = (int)B; bt->n = (int)n; bt->m = (int)m;
   bt->nnzA = (int)std::max<qpg_int>(nnzA_max, 1); bt->nnzQ = (int)std::max<qpg_int>(nnzQ_max, 1); bt->nnzQf = 2 * bt->nnzQ;
+  bt->nnzA_in = (int)nnzA_max; bt->nnzQ_in = (int)nnzQ_max;
+  bt->map_A.resize((size_t)B); bt->map_Q.resize((size_t)B);
   bt->kkt = kkt; bt->nfac = (int)nfac; bt->sparse = sparse;
   bt->ld = (int)align_up((size_t)nfac, (size_t)ctx->ld_align);
   {
@@ -405,25 +416,36 @@ static int set_problem_impl(qpg_batch *bt, qpg_int idx, qpg_int n_, qpg_int m_, 
    * rows ascending: already-sorted columns (the usual case) are copied straight, others sorted by row (stable: equal rows keep
    * the caller's order, QPS-loaded matrices may be unsorted, SURVEY App. F).  Returns the new position, -1 on a bad index. */
   std::vector<std::pair<int, double> > tmp;
-  auto take_column = [&tmp](const qpg_int *I, const qpg_float *X, qpg_int k0, qpg_int k1, qpg_int rmin, qpg_int rmax, int *di, double *dx, qpg_int pos) -> qpg_int {
+  bool reordered = false; /* some column was sorted or lost an entry: the device's order of the values is not the caller's (value_map below) */
+  auto take_column = [&tmp, &reordered](const qpg_int *I, const qpg_float *X, qpg_int k0, qpg_int k1, qpg_int rmin, qpg_int rmax, int *di, double *dx, qpg_int pos) -> qpg_int {
     bool sorted = true;
     qpg_int prev = -1;
     const qpg_int p0 = pos;
     for (qpg_int k = k0; k < k1; k++) {
       const qpg_int r = I[k];
       if (r < 0 || r >= rmax) return -1;
-      if (r < rmin) continue;
+      if (r < rmin) { reordered = true; continue; }
       if (r < prev) sorted = false;
       prev = r;
       di[pos] = (int)r; dx[pos] = X[k]; pos++;
     }
     if (!sorted) {
+      reordered = true;
       tmp.clear();
       for (qpg_int t = p0; t < pos; t++) tmp.push_back(std::make_pair(di[t], dx[t]));
       std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
       for (qpg_int t = p0; t < pos; t++) { di[t] = tmp[t - p0].first; dx[t] = tmp[t - p0].second; }
     }
     return pos;
+  };
+  /* position in the caller's arrays of every entry take_column keeps, in its order (the same stable sort, on positions); only for input it reordered */
+  auto value_map = [n](const qpg_int *Pc, const qpg_int *I, bool lower, std::vector<int> &map) {
+    map.clear();
+    for (int j = 0; j < n; j++) {
+      const size_t p0 = map.size();
+      for (qpg_int k = Pc[j]; k < Pc[j + 1]; k++) if (!lower || I[k] >= j) map.push_back((int)k);
+      std::stable_sort(map.begin() + p0, map.end(), [I](int a, int b) { return I[a] < I[b]; });
+    }
   };
   /* A: CSC with sorted rows inside each column */
   for (int j = 0; j < n; j++) {
@@ -432,6 +454,9 @@ static int set_problem_impl(qpg_batch *bt, qpg_int idx, qpg_int n_, qpg_int m_, 
     if (take_column(Ai, Ax, Ap[j], Ap[j + 1], 0, m, hAi, hAx, Ap[j]) < 0) return fail(QPG_ERR_INVALID, "A: row index out of range");
   }
   hAp[n] = (int)nzA;
+  bt->map_A[ib].clear();
+  if (reordered) value_map(Ap, Ai, false, bt->map_A[ib]);
+  reordered = false;
   pad_ptr(hAp, (size_t)n + 1, bt->hper[H_AP]); pad(hAi, (size_t)nzA, bt->hper[H_AI]); pad(hAx, (size_t)nzA, bt->hper[H_AX]);
   P.nzA = (int)nzA;
   /* A' pattern (what cholmod_transpose(A,1) builds, iteration.c:81) + permutation into A */
@@ -456,6 +481,8 @@ static int set_problem_impl(qpg_batch *bt, qpg_int idx, qpg_int n_, qpg_int m_, 
     }
     hQp[n] = (int)pos;
     P.nzQ = (int)pos;
+    bt->map_Q[ib].clear();
+    if (reordered) value_map(Qp, Qi, true, bt->map_Q[ib]);
     pad_ptr(hQp, (size_t)n + 1, bt->hper[H_QP]); pad(hQi, (size_t)pos, bt->hper[H_QI]); pad(hQx, (size_t)pos, bt->hper[H_QX]);
     /* both triangles, compressed by column (== by row), rows ascending, with the map into Q */
     std::vector<int> cnt(n + 1, 0);
@@ -933,6 +960,41 @@ extern "C" int qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, 
   return api_ok();
 }
 
+/* the per-QP scalars qpalm_setup leaves (seq_hint is the member's own) */
+static qpg_scalars setup_scalars(const qpg_batch *bt) {
+  qpg_scalars sc0;
+  memset(&sc0, 0, sizeof(sc0));
+  sc0.status = QPG_UNSOLVED; sc0.gamma = bt->settings.gamma_init; sc0.sqrt_delta = sqrt(bt->settings.delta);
+  sc0.sc_c = 1.0; sc0.sc_cinv = 1.0; sc0.kkt_first = 1; /* qpalm.c:272 */
+  sc0.kkt_na = -1;
+  return sc0;
+}
+/* set_settings_nonconvex (qpalm.c:293-296), after scale_data like the reference */
+static int run_lobpcg(qpg_batch *bt) {
+  qpg_view &V = bt->V;
+  const size_t B = bt->B, n = bt->n;
+  /* start vector of lobpcg: rand()/RAND_MAX from the C library's default state (nonconvex.c:41-44, B9).  Every QP of the
+   * batch gets the sequence a fresh process would produce (glibc TYPE_3 generator, seed 1), restated here so that the
+   * result does not depend on the host's libc or on earlier rand() calls. */
+  std::vector<double> x0(B * n, 0.0);
+  {
+    int32_t tab[344];
+    tab[0] = 1;
+    for (int i = 1; i < 31; i++) { long hi = tab[i - 1] / 127773, lo = tab[i - 1] % 127773; long v = 16807 * lo - 2836 * hi; if (v < 0) v += 2147483647; tab[i] = (int32_t)v; }
+    for (int i = 31; i < 34; i++) tab[i] = tab[i - 31];
+    for (int i = 34; i < 344; i++) tab[i] = (int32_t)((uint32_t)tab[i - 31] + (uint32_t)tab[i - 3]);
+    std::vector<uint32_t> o(344 + n);
+    for (int i = 0; i < 344; i++) o[i] = (uint32_t)tab[i];
+    for (size_t k = 0; k < n; k++) o[344 + k] = o[344 + k - 31] + o[344 + k - 3];
+    for (size_t b = 0; b < B; b++)
+      for (int k = 0; k < bt->probs[b].n; k++) x0[b * n + k] = (double)(int)(o[344 + k] >> 1) / 2147483647;
+  }
+  RT_MEMCPY_H2D(V.d, x0.data(), x0.size() * sizeof(double));
+  BT_LAUNCH(bt, k_lobpcg, blocks_for(bt), 0, V);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_lobpcg failed: " + std::string(RT_LAST_ERROR()));
+  return QPG_OK;
+}
+
 extern "C" int qpg_batch_setup(qpg_batch *bt) {
   if (!bt) return fail(QPG_ERR_INVALID, "qpg_batch_setup: NULL");
   for (int b = 0; b < bt->B; b++) if (!bt->probs[b].set) return fail(QPG_ERR_INVALID, "qpg_batch_setup: problem not set for every batch member");
@@ -946,6 +1008,8 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
   }
   bt->arena_clean = false;
   bt->is_setup = false;
+  bt->raw_q.clear(); bt->raw_bmin.clear(); bt->raw_bmax.clear(); /* the device gets the slab's q and bounds again */
+  bt->val_maps_current = false;                                  /* (the members may have been set again) */
   V.B = bt->B; V.n = bt->n; V.m = bt->m; V.ld = bt->ld; V.nnzA = bt->nnzA; V.nnzQ = bt->nnzQ; V.nnzQf = bt->nnzQf;
   V.ls_hbm = bt->ctx->linesearch_hbm; V.seq_mode = bt->ctx->sequential_rank_sums;
   V.nslots = bt->nslots; V.lds_bytes = bt->lds_bytes; V.update_rank_threshold = bt->ctx->update_rank_threshold; V.place_panel_wave = bt->ctx->place_panel_wave;
@@ -981,11 +1045,7 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
     /* ... while the copies run: the small per-QP records */
     std::vector<double> c0(B);
     std::vector<qpg_scalars> sc(B);
-    qpg_scalars sc0;
-    memset(&sc0, 0, sizeof(sc0));
-    sc0.status = QPG_UNSOLVED; sc0.gamma = bt->settings.gamma_init; sc0.sqrt_delta = sqrt(bt->settings.delta);
-    sc0.sc_c = 1.0; sc0.sc_cinv = 1.0; sc0.kkt_first = 1; /* qpalm.c:272 */
-    sc0.kkt_na = -1;
+    const qpg_scalars sc0 = setup_scalars(bt);
     for (size_t b = 0; b < B; b++) {
       c0[b] = bt->probs[b].c; sc[b] = sc0; bt->host_status[b] = QPG_UNSOLVED;
       /* a column of Q without a positive diagonal entry: H = Q + A' Sigma A + I / gamma can have pivots of the size of 1 / gamma (seq_hint) */
@@ -1021,26 +1081,9 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
   RT_MEMCPY_H2D(V.settings, &st, sizeof(st));
   BT_LAUNCH(bt, k_setup, blocks_for(bt), 0, V, (int)bt->settings.scaling, 0);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_setup failed: " + std::string(RT_LAST_ERROR()));
-  if (bt->settings.nonconvex) { /* set_settings_nonconvex (qpalm.c:293-296), after scale_data like the reference */
-    /* start vector of lobpcg: rand()/RAND_MAX from the C library's default state (nonconvex.c:41-44, B9).  Every QP of the
-     * batch gets the sequence a fresh process would produce (glibc TYPE_3 generator, seed 1), restated here so that the
-     * result does not depend on the host's libc or on earlier rand() calls. */
-    std::vector<double> x0(B * n, 0.0);
-    {
-      int32_t tab[344];
-      tab[0] = 1;
-      for (int i = 1; i < 31; i++) { long hi = tab[i - 1] / 127773, lo = tab[i - 1] % 127773; long v = 16807 * lo - 2836 * hi; if (v < 0) v += 2147483647; tab[i] = (int32_t)v; }
-      for (int i = 31; i < 34; i++) tab[i] = tab[i - 31];
-      for (int i = 34; i < 344; i++) tab[i] = (int32_t)((uint32_t)tab[i - 31] + (uint32_t)tab[i - 3]);
-      std::vector<uint32_t> o(344 + n);
-      for (int i = 0; i < 344; i++) o[i] = (uint32_t)tab[i];
-      for (size_t k = 0; k < n; k++) o[344 + k] = o[344 + k - 31] + o[344 + k - 3];
-      for (size_t b = 0; b < B; b++)
-        for (int k = 0; k < bt->probs[b].n; k++) x0[b * n + k] = (double)(int)(o[344 + k] >> 1) / 2147483647;
-    }
-    RT_MEMCPY_H2D(V.d, x0.data(), x0.size() * sizeof(double));
-    BT_LAUNCH(bt, k_lobpcg, blocks_for(bt), 0, V);
-    if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_lobpcg failed: " + std::string(RT_LAST_ERROR()));
+  if (bt->settings.nonconvex) {
+    const int rcl = run_lobpcg(bt);
+    if (rcl != QPG_OK) return rcl;
   }
   bt->is_setup = true;
   return api_ok();
@@ -1535,6 +1578,15 @@ extern "C" int qpg_batch_update_settings(qpg_batch *bt, const QPGSettings *s) { 
   return api_ok();
 }
 
+/* creates the record of the raw q / bounds from the slab (see qpg_batch) */
+static void raw_record(qpg_batch *bt) {
+  if (!bt->raw_q.empty()) return;
+  const size_t B = bt->B, n = bt->n, m = bt->m;
+  bt->raw_q.assign(bt->harr<double>(H_Q, 0), bt->harr<double>(H_Q, 0) + B * n);
+  bt->raw_bmin.assign(bt->harr<double>(H_BMIN, 0), bt->harr<double>(H_BMIN, 0) + B * m);
+  bt->raw_bmax.assign(bt->harr<double>(H_BMAX, 0), bt->harr<double>(H_BMAX, 0) + B * m);
+}
+
 extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, const qpg_float *bmax) { /* qpalm.c:793-827 */
   NEED_SETUP(bt, "qpg_batch_update_bounds");
   const size_t B = bt->B, m = bt->m, ls = (size_t)bt->ls_stride;
@@ -1550,7 +1602,12 @@ extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, con
   std::vector<int> bad(B, 0);
   RT_MEMCPY_D2H(bad.data(), bad_d, B * sizeof(int));
   int nbad = 0;
+  raw_record(bt);
   for (size_t b = 0; b < B; b++) {
+    if (!bad[b] && m > 0) { /* accepted: the member's raw bounds from now on (qpg_batch_update_Q_A) */
+      if (bmin) memcpy(bt->raw_bmin.data() + b * m, bmin + b * m, m * sizeof(double));
+      if (bmax) memcpy(bt->raw_bmax.data() + b * m, bmax + b * m, m * sizeof(double));
+    }
     if (bad[b]) { bt->host_status[b] = QPG_ERROR; nbad++; }
     else if (bt->host_status[b] == QPG_ERROR) bt->host_status[b] = QPG_UNSOLVED; /* valid bounds now: qpalm_solve overwrites the status (qpalm.c:401-420) */
   }
@@ -1564,7 +1621,69 @@ extern "C" int qpg_batch_update_q(qpg_batch *bt, const qpg_float *q) { /* qpalm.
   RT_MEMCPY_H2D(bt->V.q, q, (size_t)bt->B * bt->n * sizeof(double));
   BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_q failed: " + std::string(RT_LAST_ERROR()));
+  raw_record(bt);
+  memcpy(bt->raw_q.data(), q, (size_t)bt->B * bt->n * sizeof(double));
   return api_ok();
+}
+
+/* qpalm_update_Q_A for every member: new values of Q and A on the patterns the batch was set up with.  Afterwards the batch is what qpg_batch_setup
+ * would leave for these values, the latest accepted raw q / bounds and the current settings -- without the host-side conversion, the symbolic
+ * analysis of the sparse factors, the pattern uploads or a new arena.  Kept: the arena, the factor and LD_Q slots, nq / mq, the settings block, the
+ * sparse symbolic state (sparse_adj_* / sparse_analyze read patterns only: an entry whose new value is 0 stays an entry), the stored solutions and the
+ * recorded coop launch chains (they hold pointers and sizes, no values).  dQx / dAx: device arrays [B][nnzQ_max] / [B][nnzA_max] in the caller's
+ * order of qpg_batch_set_problem*; strideQ / strideA: doubles between two members in them. */
+static int update_Q_A_device(qpg_batch *bt, const double *dQx, size_t strideQ, const double *dAx, size_t strideA) {
+  qpg_view &V = bt->V;
+  const size_t B = bt->B, n = bt->n, m = bt->m, zA = bt->nnzA, zQ = bt->nnzQ;
+  int32_t *mapA_d = nullptr, *mapQ_d = nullptr, *same_d = nullptr;
+  bool any_map = false;
+  for (size_t b = 0; b < B && !any_map; b++) any_map = !bt->map_A[b].empty() || !bt->map_Q[b].empty();
+  if (any_map) {
+    const size_t oQ = align_up(B * zA * 4, 256), oS = oQ + align_up(B * zQ * 4, 256), bytes = oS + B * 2 * 4;
+    if (!bt->val_maps_d && RT_MALLOC(&bt->val_maps_d, bytes) != 0) { bt->val_maps_d = nullptr; return fail(QPG_ERR_ALLOC, "device allocation failed (value maps)"); }
+    mapA_d = (int32_t *)bt->val_maps_d; mapQ_d = (int32_t *)((char *)bt->val_maps_d + oQ); same_d = (int32_t *)((char *)bt->val_maps_d + oS);
+    if (!bt->val_maps_current) {
+      std::vector<int32_t> same(B * 2);
+      for (size_t b = 0; b < B; b++) {
+        same[2 * b] = bt->map_A[b].empty() ? 1 : 0; same[2 * b + 1] = bt->map_Q[b].empty() ? 1 : 0;
+        if (!same[2 * b]) RT_MEMCPY_H2D(mapA_d + b * zA, bt->map_A[b].data(), bt->map_A[b].size() * 4);
+        if (!same[2 * b + 1]) RT_MEMCPY_H2D(mapQ_d + b * zQ, bt->map_Q[b].data(), bt->map_Q[b].size() * 4);
+      }
+      RT_MEMCPY_H2D(same_d, same.data(), same.size() * 4);
+      bt->val_maps_current = true;
+    }
+  }
+  /* the raw q and bounds a fresh setup would upload */
+  const bool rec = !bt->raw_q.empty();
+  RT_MEMCPY_H2D(V.q, rec ? bt->raw_q.data() : bt->harr<double>(H_Q, 0), B * n * sizeof(double));
+  if (m > 0) {
+    RT_MEMCPY_H2D(V.bmin, rec ? bt->raw_bmin.data() : bt->harr<double>(H_BMIN, 0), B * m * sizeof(double));
+    RT_MEMCPY_H2D(V.bmax, rec ? bt->raw_bmax.data() : bt->harr<double>(H_BMAX, 0), B * m * sizeof(double));
+  }
+  BT_LAUNCH(bt, k_update_Q_A, blocks_for(bt), 0, V, dQx, (long long)strideQ, dAx, (long long)strideA, (const int32_t *)mapQ_d, (const int32_t *)mapA_d,
+            (const int32_t *)same_d, setup_scalars(bt), (int)bt->settings.scaling);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_Q_A failed: " + std::string(RT_LAST_ERROR()));
+  if (bt->settings.nonconvex) {
+    const int rcl = run_lobpcg(bt);
+    if (rcl != QPG_OK) return rcl;
+  }
+  std::fill(bt->host_status.begin(), bt->host_status.end(), QPG_UNSOLVED);
+  return api_ok();
+}
+extern "C" int qpg_batch_update_Q_A_device(qpg_batch *bt, const qpg_float *dQx, const qpg_float *dAx) {
+  NEED_SETUP(bt, "qpg_batch_update_Q_A_device");
+  if (!dQx || !dAx) return fail(QPG_ERR_INVALID, "qpg_batch_update_Q_A_device: NULL");
+  return update_Q_A_device(bt, dQx, (size_t)bt->nnzQ_in, dAx, (size_t)bt->nnzA_in);
+}
+extern "C" int qpg_batch_update_Q_A(qpg_batch *bt, const qpg_float *Qx, const qpg_float *Ax) {
+  NEED_SETUP(bt, "qpg_batch_update_Q_A");
+  if (!Qx || !Ax) return fail(QPG_ERR_INVALID, "qpg_batch_update_Q_A: NULL");
+  /* staged in the arrays of derived values, which the kernel rebuilds after it has read them: A's values where the member's A' values go, Q's at the
+   * start of the member's full-Q values (a stride of 2 nnzQ: no workgroup writes where another still reads) */
+  const size_t B = bt->B;
+  if (bt->nnzA_in > 0) RT_MEMCPY_H2D(bt->V.Atx, Ax, B * (size_t)bt->nnzA_in * sizeof(double));
+  if (bt->nnzQ_in > 0) RT_MEMCPY2D_H2D(bt->V.Qfx, (size_t)bt->nnzQf * sizeof(double), Qx, (size_t)bt->nnzQ_in * sizeof(double), (size_t)bt->nnzQ_in * sizeof(double), B);
+  return update_Q_A_device(bt, bt->V.Qfx, (size_t)bt->nnzQf, bt->V.Atx, (size_t)bt->nnzA);
 }
 
 extern "C" void qpg_batch_destroy(qpg_batch *bt) {
@@ -1574,6 +1693,7 @@ extern "C" void qpg_batch_destroy(qpg_batch *bt) {
   if (bt->dual_d) RT_FREE(bt->dual_d);
   if (bt->sparse_d) RT_FREE(bt->sparse_d);
   if (bt->co_tab_d) RT_FREE(bt->co_tab_d);
+  if (bt->val_maps_d) RT_FREE(bt->val_maps_d);
   co_graphs_clear(bt);
   host_slab_free(bt->hslab, bt->hslab_bytes);
   delete bt;

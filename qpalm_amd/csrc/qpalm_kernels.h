@@ -72,6 +72,63 @@ __global__ __launch_bounds__(QP_T) void k_setup(qpg_view V, int nscale, int mode
 }
 
 
+/* qpalm_update_Q_A, device part: new values of Q and A on the patterns the batch was set up with; afterwards the QP is what k_setup
+ * (mode 0) leaves after a fresh upload.  The host wrote the raw q / bmin / bmax into place.  Qnew / Anew: the new values in the order of
+ * the arrays the caller passed to qpg_batch_set_problem* (member b at b * strideQ / b * strideA); mapQ / mapA ([B][nnzQ] / [B][nnzA]): the
+ * position in them of every entry of Qx / Ax, for the members whose same[2 b + 1] / same[2 b] is 0 (NULL: the same order everywhere).
+ * sc0: the scalars of a fresh setup.  The stored solution (sol_x, sol_y) stays. */
+__global__ __launch_bounds__(QP_T) void k_update_Q_A(qpg_view V, const double *Qnew, long long strideQ, const double *Anew, long long strideA,
+                                                     const int32_t *mapQ, const int32_t *mapA, const int32_t *same, qpg_scalars sc0, int nscale) {
+  __shared__ IterShared I;
+  const int tid = threadIdx.x;
+  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+    const QpArrays a = qp_arrays(V, b);
+    const int n = a.n, nzA = QP_UNIFORM(a.Ap()[n]), nzQ = QP_UNIFORM(a.Qp()[n]), nzQf = QP_UNIFORM(a.Qfp()[n]);
+    __syncthreads();
+    { /* the values, from the caller's order */
+      const double *srcA = Anew + (size_t)b * strideA, *srcQ = Qnew + (size_t)b * strideQ;
+      const int sameA = same ? QP_UNIFORM(same[2 * b]) : 1, sameQ = same ? QP_UNIFORM(same[2 * b + 1]) : 1;
+      const int32_t *mA = mapA + (size_t)b * V.nnzA, *mQ = mapQ + (size_t)b * V.nnzQ;
+      for (int k = tid; k < nzA; k += QP_T) a.Ax()[k] = sameA ? srcA[k] : srcA[mA[k]];
+      for (int k = tid; k < nzQ; k += QP_T) a.Qx()[k] = sameQ ? srcQ[k] : srcQ[mQ[k]];
+    }
+    __syncthreads(); /* (the staged values may sit where the derived ones go: everything is read before anything below is written) */
+    { /* the work vectors as the cleared arena of a fresh setup holds them (whole strides) */
+      const size_t sn = V.n, sm = V.m, bb = (size_t)b;
+      double *const vn[] = {V.x, V.Qxv, V.Aty, V.x_prev, V.x0, V.Atyh, V.df, V.dphi, V.dphi_prev, V.d, V.Qd, V.delta_x, V.temp_n, V.D, V.Dinv, V.dual_rhs};
+      double *const vm[] = {V.y, V.Axv, V.sigma, V.sigma_inv, V.sqrt_sigma, V.At_scale, V.Axys, V.z, V.pri_res, V.pri_res_in, V.yh, V.Ad, V.delta_y,
+                            V.temp_m, V.E, V.Einv};
+      int32_t *const im[] = {V.active, V.active_old, V.enter, V.leave};
+      for (double *p : vn) for (size_t j = tid; j < sn; j += QP_T) p[bb * sn + j] = 0.0;
+      for (double *p : vm) for (size_t i = tid; i < sm; i += QP_T) p[bb * sm + i] = 0.0;
+      for (int32_t *p : im) for (size_t i = tid; i < sm; i += QP_T) p[bb * sm + i] = 0;
+      for (size_t i = tid; i < (size_t)V.ls_stride; i += QP_T) { V.ls_key[bb * V.ls_stride + i] = 0.0; V.ls_idx[bb * V.ls_stride + i] = 0; }
+      for (size_t i = tid; i < 2 * sm; i += QP_T) { V.ls_delta[bb * 2 * sm + i] = 0.0; V.ls_alpha[bb * 2 * sm + i] = 0.0; }
+      for (size_t k = tid; k < (size_t)V.nnzA; k += QP_T) { V.Atss[bb * V.nnzA + k] = 0.0; V.Atx[bb * V.nnzA + k] = 0.0; }
+      for (size_t k = tid; k < (size_t)V.nnzQf; k += QP_T) V.Qfx[bb * V.nnzQf + k] = 0.0;
+      if (V.kkt) {
+        const size_t sk = sn + sm;
+        for (size_t i = tid; i < sk; i += QP_T) { V.kkt_sol[bb * sk + i] = 0.0; V.kkt_rhs[bb * sk + i] = 0.0; V.kkt_tmp[bb * sk + i] = 0.0; V.kkt_rhs2[bb * sk + i] = 0.0; }
+        for (size_t i = tid; i < sm; i += QP_T) { V.kkt_state[bb * sm + i] = 0; V.kkt_list[bb * sm + i] = 0; }
+      }
+    }
+    /* seq_hint: a column of Q without a positive diagonal entry (qpg_batch_setup finds it on the host, from the same raw values) */
+    int bare = 0;
+    for (int j = tid; j < n; j += QP_T) {
+      bool pos = false;
+      for (int k = a.Qp()[j]; k < a.Qp()[j + 1]; k++) if (a.Qi()[k] == j && a.Qx()[k] > 0.0) pos = true;
+      if (!pos) bare = 1;
+    }
+    const int hint = block_isum(I.S, bare) > 0 ? 1 : 0; /* (its barriers also order the clearing above before dev_scale_data) */
+    if (tid == 0) { I.s = sc0; I.s.seq_hint = hint; I.s.has_scaling = nscale > 0 ? 1 : 0; }
+    __syncthreads();
+    if (nscale > 0) dev_scale_data(V, a, b, nscale, I);
+    dev_fill_derived(V, a, b);
+    if (tid == 0) V.sc[b] = I.s;
+    __syncthreads();
+  }
+}
+
 /* =============================================================================================
  * set_settings_nonconvex + lobpcg (src/nonconvex.c:29-183), one workgroup per QP, at setup time (qpalm.c:293-296).
  * LOBPCG stops on ||A x - lambda x||_inf < 1e-5, so its iteration count -- and with it gamma = 1/|lambda| and every

@@ -271,6 +271,44 @@ void qpalm_update_q(QPALMWorkspace *work, const c_float *q) { /* qpalm.c:829-871
   set_status(work->info, status);
 }
 
+/* the device keeps a column's rows ascending and the lower triangle of Q: is that the order of M's own arrays? */
+static int device_order(const solver_sparse *M, int lower) {
+  const c_int *Mp = (const c_int *)M->p, *Mi = (const c_int *)M->i;
+  for (size_t j = 0; j < M->ncol; j++)
+    for (c_int k = Mp[j]; k < Mp[j + 1]; k++)
+      if ((lower && Mi[k] < (c_int)j) || (k > Mp[j] && Mi[k] < Mi[k - 1])) return 0;
+  return 1;
+}
+
+/* upstream QPALM's qpalm_update_Q_A (the reference snapshot predates it): new values of Q and A on the workspace's patterns, in the order of the
+ * data->Q->x / data->A->x the workspace was set up with.  The device rescales and starts over as after qpalm_setup (qpg_batch_update_Q_A); the
+ * workspace mirrors follow: data->Q->x and data->A->x hold the scaled values as after qpalm_setup (the raw ones where the device keeps another
+ * order than the caller's), scaling and the iterates as the device has them. */
+void qpalm_update_Q_A(QPALMWorkspace *work, const c_float *Qx, const c_float *Ax) {
+  if (qpg_batch_update_Q_A(BT(work), Qx, Ax) != QPG_OK) {
+    snprintf(g_host_err, sizeof g_host_err, "%s", qpg_last_error());
+    set_status(work->info, QPALM_ERROR);
+    return;
+  }
+  const size_t n = work->data->n;
+  const size_t nzA = (size_t)((c_int *)work->data->A->p)[n], nzQ = (size_t)((c_int *)work->data->Q->p)[n];
+  memcpy(work->data->A->x, Ax, nzA * sizeof(c_float));
+  memcpy(work->data->Q->x, Qx, nzQ * sizeof(c_float));
+  const int A_same = device_order(work->data->A, 0);
+  pull(work); /* (reads A's values in the device's order) */
+  if (!A_same) memcpy(work->data->A->x, Ax, nzA * sizeof(c_float));
+  if (device_order(work->data->Q, 1)) getv(work, "Q_values", (c_float *)work->data->Q->x, nzQ);
+  work->initialized = FALSE;
+  if (work->settings->nonconvex) { /* set_settings_nonconvex ran again on the new Q */
+    QPGStats gs;
+    if (qpg_batch_get_stats(BT(work), 0, &gs) == QPG_OK && gs.nonconvex) {
+      work->settings->gamma_init = 1 / (gs.lobpcg_lambda < 0 ? -gs.lobpcg_lambda : gs.lobpcg_lambda);
+      work->settings->gamma_max = work->settings->gamma_init;
+    }
+  }
+  set_status(work->info, QPALM_UNSOLVED);
+}
+
 void qpalm_cleanup(QPALMWorkspace *work) { /* qpalm.c:874-1096 */
   if (!work) return;
   if (work->data) {

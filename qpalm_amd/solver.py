@@ -94,6 +94,7 @@ class QpalmBatch:
         self.dims = [(int(p.n), int(p.m)) for p in problems]   # members may be smaller than the batch (mixed sizes)
         nnzA = max(int(p.Ap[-1]) for p in problems)
         nnzQ = max(int(p.Qp[-1]) for p in problems)
+        self.nnzA, self.nnzQ = nnzA, nnzQ   # row lengths of the arrays update_Q_A takes
         self.settings = settings if settings is not None else ctx.default_settings()
         h = C.c_void_p()
         import time
@@ -185,6 +186,34 @@ class QpalmBatch:
     def update_q(self, q):
         q = f64(q).reshape(self.B, self.n)
         self._check(self.L.qpg_batch_update_q(self.h, fptr(q)))
+
+    def _padded(self, v, width):
+        """[B][width] float64 from an array of that shape or a list of per-member arrays (padded with zeros)"""
+        if isinstance(v, np.ndarray) and v.ndim == 2:
+            out = f64(v)
+            if out.shape != (self.B, width):
+                raise ValueError("expected an array of shape %r, got %r" % ((self.B, width), out.shape))
+            return out
+        if len(v) != self.B:
+            raise ValueError("expected %d per-member arrays, got %d" % (self.B, len(v)))
+        out = np.zeros((self.B, width))
+        for b, row in enumerate(v):
+            row = f64(row).ravel()
+            if len(row) > width:
+                raise ValueError("member %d: %d values, the batch holds at most %d" % (b, len(row), width))
+            out[b, :len(row)] = row
+        return out
+
+    def update_Q_A(self, Qx, Ax):
+        """qpalm_update_Q_A: new values of Q and A on the patterns the batch was set up with, each member's in the order of the Qx / Ax its problem was
+        given with.  [B][nnzQ_max] / [B][nnzA_max] arrays, or lists of per-member arrays.  The batch is then what a fresh setup with these values, the
+        latest q / bounds and the current settings would be; the stored solutions stay (warm_start_last)."""
+        q, a = self._padded(Qx, self.nnzQ), self._padded(Ax, self.nnzA)
+        self._check(self.L.qpg_batch_update_Q_A(self.h, fptr(q), fptr(a)))
+
+    def update_Q_A_device(self, ptr_Qx, ptr_Ax):
+        """the same from device memory: raw addresses of [B][nnzQ_max] / [B][nnzA_max] float64 arrays (e.g. torch tensors' data_ptr())"""
+        self._check(self.L.qpg_batch_update_Q_A_device(self.h, C.c_void_p(int(ptr_Qx)), C.c_void_p(int(ptr_Ax))))
 
     # -- results --------------------------------------------------------------------------------
     def info(self, b=0):
@@ -377,6 +406,10 @@ class Qpalm:
 
     def update_q(self, q):
         self._batch.update_q(f64(q)[None, :])
+
+    def update_Q_A(self, Qx, Ax):
+        """new values of Q and A (same patterns), in the order of the problem's own Qx / Ax"""
+        self._batch.update_Q_A([f64(Qx)], [f64(Ax)])
 
     @property
     def info(self):
