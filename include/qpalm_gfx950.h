@@ -164,6 +164,13 @@ void qpg_ctx_destroy(qpg_ctx *ctx);
  *   "sparse_lds"            1 (default) = the sparse factorisation accumulates a column, the sparse solves keep the right-hand side and the path
  *                           updates their work vector in LDS where they fit; 0 = the forms on vectors in HBM (same iterates bit for bit: A/B and
  *                           tests); >= 2 = LDS only for columns of at most that many entries (tests)
+ *   "sparse_coop"           0 (default) = the factor operations of a sparse QP run on the QP's own workgroup; 1 = a batch that keeps the sparse
+ *                           Schur factor, has at most "coop_max_batch" members and B <= "max_slots" runs its factorisations and Newton solves
+ *                           (what the reference hands to CHOLMOD's factorize and solve, solver_interface.c:319-370, 505-519) on up to
+ *                           "coop_workgroups" workgroups: the levels of the elimination tree become a chain of launches
+ *                           (qpg_batch_sparse_coop_info below), replayed as graphs under "coop_graphs".  Every other batch -- "sparse_kkt",
+ *                           larger batches, dense factors -- runs as with 0.  Path updates stay on the QP's workgroup.  Read by
+ *                           qpg_batch_setup.  Same iterates bit for bit; "coop" does not switch this on, and nothing does by itself.
  *   "coop", "coop_workgroups", "coop_updates", "coop_rank_threshold"   one large QP on many workgroups
  * Environment: QPALM_HOST_THREADS = host threads of qpg_batch_set_problems (default: hardware threads, at most 24). */
 int  qpg_ctx_set_option(qpg_ctx *ctx, const char *name, qpg_int value);
@@ -221,6 +228,15 @@ int  qpg_batch_sparse_info(qpg_batch *bt, qpg_int idx, qpg_int *nnzL, qpg_int *d
  * at least four times shallower -- the factorisation and the solves run at the latency of the tree's height.  Changes rounding, not
  * what is computed. */
 int  qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, qpg_int *levels);
+/* The launch plan of member idx under the context option "sparse_coop" = 1, made by qpg_batch_setup from the level sets of the member's
+ * elimination tree (patterns only: qpg_batch_update_Q_A leaves it valid): launches per factorisation, launches per Newton solve (permutation in,
+ * forward levels, D, backward levels, permutation out) and the largest grid among them.  Consecutive levels that one workgroup finishes in one
+ * round (64 columns of the factorisation at the default "sparse_gpw", 512 rows of a solve) share ONE launch on one workgroup -- a band under the
+ * natural ordering is one launch per phase --, a wider level is a launch of its own on min(G, ceil(width / round)) workgroups; G = "coop_workgroups"
+ * (at most 1024 / B), fewer while the zeroed work vectors of those workgroups and of the resident slots together would exceed 4 GB (G = 1: one
+ * launch per phase).  All three are 0 when the batch runs on one
+ * workgroup per QP; QPG_ERR_UNSUPPORTED on a batch with dense factors. */
+int  qpg_batch_sparse_coop_info(qpg_batch *bt, qpg_int idx, qpg_int *factor_launches, qpg_int *solve_launches, qpg_int *max_grid);
 int  qpg_batch_update_settings(qpg_batch *bt, const QPGSettings *s);
 int  qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, const qpg_float *bmax); /* [B][m] or NULL */
 int  qpg_batch_update_q(qpg_batch *bt, const qpg_float *q);                              /* [B][n] */

@@ -93,6 +93,8 @@ def load(path=None):
         L.qpg_batch_sparse_info.argtypes = [C.c_void_p, c_int, pi, pi]
     if hasattr(L, "qpg_batch_sparse_perm"):   # (absent from older builds of the library that tools/evidence/gpu_ab.sh compares with)
         L.qpg_batch_sparse_perm.argtypes = [C.c_void_p, c_int, pi, pi]
+    if hasattr(L, "qpg_batch_sparse_coop_info"):   # (absent from older builds of the library that tools/evidence/sparse_coop_timing.py compares with)
+        L.qpg_batch_sparse_coop_info.argtypes = [C.c_void_p, c_int, pi, pi, pi]
     L.qpg_batch_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.qpg_batch_update_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
     L.qpg_batch_update_bounds.argtypes = [C.c_void_p, pf, pf]
@@ -149,7 +151,7 @@ SYMBOLS = [
     "qpg_exact_linesearch", "qpg_batch_ldlsolve_all", "qpg_batch_sweep_probe", "qpg_kkt_form", "qpg_kkt_factorize",
     "qpg_kkt_update_entering_constraints", "qpg_kkt_update_leaving_constraints", "qpg_kkt_solve", "qpg_ldlchol_matrix", "qpg_sparse_matvec",
     "qpg_batch_begin_solve", "qpg_batch_get_info_all", "qpg_batch_get_stats_all", "qpg_ctx_hbm_copy_gbs", "qpg_ctx_hbm_read_gbs", "qpg_host_alloc", "qpg_host_free", "qpg_batch_set_problem_sized", "qpg_batch_set_problems",
-    "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device",
+    "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device", "qpg_batch_sparse_coop_info",
 ]
 
 

@@ -133,6 +133,9 @@ struct qpg_ctx {
                               -1 (default): dissection where the natural tree is deep and the dissected one at least four times shallower */
   int sparse_factor;       /* -1 (default): the sparse L D L' (qpalm_sparse.h) for factors of more than 8192 rows, the dense panel otherwise; 1: sparse
                               whenever the mode allows it (Schur path); 0: never (larger factors are refused) */
+  int sparse_coop;         /* 0 (default): a sparse QP's factor operations run on its own workgroup; 1: a batch that keeps the sparse Schur factor, has at most
+                              coop_max_batch members and B <= max_slots runs its factorisations and Newton solves on up to coop_workgroups workgroups
+                              (sparse_coop_plan, coop_solve); read by qpg_batch_setup.  Path updates stay on the QP's workgroup.  The option "coop" does not switch this on */
   int sparse_kkt;          /* 0 (default): FACTORIZE_KKT keeps the dense (n+m) x (n+m) panel (more than 8192 rows are refused); 1: every KKT batch keeps a
                               sparse L D L' of K (qpalm_sparse_kkt.h), whatever its size */
   int ld_align;            /* leading dimension of the factor panels = rows rounded up to this many doubles.  16 (default): every column starts on a
@@ -175,6 +178,11 @@ struct qpg_batch {
   void *sparse_d; size_t sparse_d_bytes; /* symbolic arrays of every member + values / work vectors of every slot */
   std::vector<long long> sp_nnz; /* nnz(L) of every member (qpg_batch_sparse_info) */
   std::vector<int> sp_levels, sp_perm; /* height of every member's elimination tree; [B][n] ordering of its factor (qpg_batch_sparse_perm) */
+  /* sparse coop mode: every member's launch plan (sparse_coop_plan; empty: the batch runs on one workgroup per QP).  A launch covers the levels
+   * [lev0, lev1) of the elimination tree on `grid` workgroups: more than one level only with grid = 1 */
+  struct SpLaunch { int lev0, lev1, grid; };
+  struct SpPlan { std::vector<SpLaunch> factor, solve; int vec_grid, solve_launches, max_grid; }; /* vec_grid: workgroups of the solve's elementwise launches */
+  std::vector<SpPlan> sp_plan;
   qpg_view V;
   bool is_setup;
   float last_solve_ms;
@@ -206,7 +214,7 @@ extern "C" int qpg_ctx_create(int device, qpg_ctx **out) {
   std::string why;
   if (RT_DEVICE_INIT(device, why) != 0) return fail(QPG_ERR_NO_DEVICE, "qpg_ctx_create: " + why);
   qpg_ctx *c = new qpg_ctx();
-  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->sparse_factor = -1; c->sparse_kkt = 0; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
+  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->sparse_factor = -1; c->sparse_kkt = 0; c->sparse_coop = 0; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
   for (int k = 0; k < 5; k++) { c->mv_buf[k] = nullptr; c->mv_cap[k] = 0; }
   *out = c;
   return api_ok();
@@ -246,6 +254,7 @@ extern "C" int qpg_ctx_set_option(qpg_ctx *ctx, const char *name, qpg_int value)
   else if (!strcmp(name, "kkt_compact")) ctx->kkt_compact = value ? 1 : 0;
   else if (!strcmp(name, "sparse_factor")) ctx->sparse_factor = (value < 0) ? -1 : (value ? 1 : 0);
   else if (!strcmp(name, "sparse_kkt")) ctx->sparse_kkt = value ? 1 : 0;
+  else if (!strcmp(name, "sparse_coop")) { if (value != 0 && value != 1) return fail(QPG_ERR_INVALID, "sparse_coop must be 0 or 1"); ctx->sparse_coop = (int)value; }
   else if (!strcmp(name, "sequential_rank_sums")) ctx->sequential_rank_sums = (value < 0) ? -1 : (value ? 1 : 0);
   else if (!strcmp(name, "linesearch_hbm")) ctx->linesearch_hbm = (value < 0) ? 0 : (int)std::min<qpg_int>(value, 1 << 20); /* >= 2: also caps the tile (a power of two): small QPs then exercise several tiles and the HBM steps between them */
   else if (!strcmp(name, "sparse_gpw")) ctx->sparse_gpw = (int)value;
@@ -829,6 +838,33 @@ static int sparse_analyze(const int n, const Cols &cols, SparseSym &S, size_t ma
     for (int j = 0; j < n; j++) S.levcol[cur[level[j]]++] = j; }
   return 0;
 }
+/* Sparse coop mode: the launch plan of one member from the level sets of its elimination tree (patterns only: qpg_batch_update_Q_A leaves it valid).
+ * Consecutive levels that one workgroup finishes in one round (at most `round_f` columns for the factorisation, `round_s` rows for the solves) become ONE
+ * launch on one workgroup, which runs the one-workgroup loop with its barriers -- a band under the natural ordering (n one-column levels) is one launch;
+ * a wider level is a launch of its own on min(G, ceil(width / round)) workgroups, grid-strided where it is wider than the grid.  G = 1 (no memory for
+ * a second workgroup's work vectors): one launch per phase. */
+static void sparse_coop_plan(const std::vector<int> &levptr, int nlev, int n, int round_f, int round_s, int G, qpg_batch::SpPlan &P) {
+  auto cut = [&](int round, std::vector<qpg_batch::SpLaunch> &out) {
+    out.clear();
+    if (G <= 1) round = 0x7fffffff; /* no grid to spread a level over: the whole phase is one launch of the one-workgroup loop, not a launch per wide level */
+    for (int l = 0; l < nlev;) {
+      const int w = levptr[(size_t)l + 1] - levptr[(size_t)l];
+      if (w > round) { out.push_back({l, l + 1, std::min(G, (w + round - 1) / round)}); l++; continue; }
+      int l1 = l + 1;
+      while (l1 < nlev && levptr[(size_t)l1 + 1] - levptr[(size_t)l1] <= round) l1++;
+      out.push_back({l, l1, 1});
+      l = l1;
+    }
+  };
+  cut(round_f, P.factor);
+  cut(round_s, P.solve);
+  P.vec_grid = std::max(1, std::min(G, (n + round_s - 1) / round_s));
+  /* permute in, forward launches, D, backward launches; level 0 on a grid: the permutation back is a launch of its own */
+  P.solve_launches = 2 + 2 * (int)P.solve.size() + ((!P.solve.empty() && P.solve[0].grid > 1) ? 1 : 0);
+  P.max_grid = P.vec_grid;
+  for (auto &l : P.factor) P.max_grid = std::max(P.max_grid, l.grid);
+  for (auto &l : P.solve) P.max_grid = std::max(P.max_grid, l.grid);
+}
 /* analysis of every member (host threads), one device block for the symbolic arrays of all members and the values / work vectors of
  * all slots, upload */
 static int sparse_setup(qpg_batch *bt) {
@@ -894,6 +930,16 @@ static int sparse_setup(qpg_batch *bt) {
   while (gpw > 1 && ns * (size_t)nw * gpw * n * 8 > ((size_t)4 << 30)) gpw >>= 1;
   V.sp_gpw = gpw; V.sp_lds = bt->ctx->sparse_lds;
   const size_t oLx = take(ns * nzmax * 8), oWv = take(ns * (size_t)nw * gpw * n * 8), oTmp = take(ns * n * 8);
+  /* sparse coop mode: G workgroups per launch as in coop_linear_algebra (the members' chains run side by side), fewer while the work vectors of the HBM
+   * form of a column -- one zeroed n-vector per group of lanes per workgroup per member -- would not fit what the slots' own work vectors (sp_wv above)
+   * leave of the SAME 4 GB: the two together stay under it (columns in the LDS form need no vector) */
+  int coG = 0;
+  if (bt->ctx->sparse_coop == 1 && !kkt && bt->threads == QP_T && bt->B <= bt->ctx->coop_max_batch && bt->B <= bt->nslots) {
+    coG = std::max(8, std::min(bt->ctx->coop_workgroups, 1024 / std::max(1, bt->B)));
+    const size_t per = B * (size_t)nw * gpw * n * 8, own = ns * (size_t)nw * gpw * n * 8, left = (own < ((size_t)4 << 30)) ? ((size_t)4 << 30) - own : 0;
+    coG = (int)std::max<size_t>(1, std::min<size_t>((size_t)coG, left / std::max<size_t>(per, 1)));
+  }
+  const size_t oCoWv = take(B * (size_t)coG * nw * gpw * n * 8);
   if (bt->sparse_d && bt->sparse_d_bytes < off) { RT_FREE(bt->sparse_d); bt->sparse_d = nullptr; }
   if (!bt->sparse_d) { if (RT_MALLOC(&bt->sparse_d, off) != 0) { bt->sparse_d = nullptr; return fail(QPG_ERR_ALLOC, "device allocation failed (sparse factor: " + std::to_string(off >> 20) + " MB)"); } bt->sparse_d_bytes = off; }
   char *base = (char *)bt->sparse_d;
@@ -902,6 +948,12 @@ static int sparse_setup(qpg_batch *bt) {
   V.sp_Lp = (int32_t *)(base + oLp); V.sp_Li = (int32_t *)(base + oLi); V.sp_Rp = (int32_t *)(base + oRp); V.sp_Rk = (int32_t *)(base + oRk);
   V.sp_Rpos = (int32_t *)(base + oRpos); V.sp_levptr = (int32_t *)(base + oLev); V.sp_levcol = (int32_t *)(base + oCol); V.sp_nlev = (int32_t *)(base + oNlev);
   V.sp_Lx = (double *)(base + oLx); V.sp_wv = (double *)(base + oWv); V.sp_tmp = (double *)(base + oTmp);
+  V.sp_co_G = coG; V.sp_co_wv = coG ? (double *)(base + oCoWv) : nullptr;
+  bt->sp_plan.clear();
+  if (coG) {
+    bt->sp_plan.resize(B);
+    for (size_t b = 0; b < B; b++) sparse_coop_plan(sym[b].levptr, sym[b].nlev, bt->probs[b].n, nw * gpw, bt->threads, coG, bt->sp_plan[b]);
+  }
   V.sp_perm = (int32_t *)(base + oPerm); V.sp_AtiP = (int32_t *)(base + oAtiP); V.sp_QfiP = (int32_t *)(base + oQfiP); V.sp_first = (int32_t *)(base + oFirst);
   std::vector<int> nlev(B);
   std::vector<int> atip(zA), qfip(zF), first(m);
@@ -944,6 +996,19 @@ extern "C" int qpg_batch_sparse_info(qpg_batch *bt, qpg_int idx, qpg_int *nnzL, 
   if (idx < 0 || idx >= bt->B) return fail(QPG_ERR_INVALID, "qpg_batch_sparse_info: bad index");
   if (nnzL) *nnzL = (qpg_int)bt->sp_nnz[(size_t)idx];
   if (device_bytes) *device_bytes = (qpg_int)bt->sparse_d_bytes;
+  return api_ok();
+}
+
+/* the launch plan of one member in sparse coop mode: launches per factorisation, launches per Newton solve, the largest grid among them; all zero when
+ * the batch runs on one workgroup per QP (QPG_ERR_UNSUPPORTED in the dense modes) */
+extern "C" int qpg_batch_sparse_coop_info(qpg_batch *bt, qpg_int idx, qpg_int *factor_launches, qpg_int *solve_launches, qpg_int *max_grid) {
+  if (!bt || !bt->is_setup) return fail(QPG_ERR_INVALID, "qpg_batch_sparse_coop_info: batch is not set up");
+  if (!bt->sparse) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_sparse_coop_info: the batch keeps dense factors");
+  if (idx < 0 || idx >= bt->B) return fail(QPG_ERR_INVALID, "qpg_batch_sparse_coop_info: bad index");
+  const bool on = !bt->sp_plan.empty();
+  if (factor_launches) *factor_launches = on ? (qpg_int)bt->sp_plan[(size_t)idx].factor.size() : 0;
+  if (solve_launches) *solve_launches = on ? (qpg_int)bt->sp_plan[(size_t)idx].solve_launches : 0;
+  if (max_grid) *max_grid = on ? (qpg_int)bt->sp_plan[(size_t)idx].max_grid : 0;
   return api_ok();
 }
 
@@ -1025,7 +1090,8 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
   V.kkt_compact = bt->ctx->kkt_compact;
   V.kkt = bt->kkt; V.nfac = bt->nfac;
   if (ensure_dual_slots(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (LD_Q slots)");
-  V.sparse = 0;
+  V.sparse = 0; V.sp_co_G = 0; V.sp_co_wv = nullptr;
+  bt->sp_plan.clear();
   if (bt->sparse) {
     const int rcs = sparse_setup(bt);
     if (rcs != QPG_OK) return rcs;
@@ -1173,6 +1239,8 @@ static bool coop_wanted(const qpg_batch *bt) {
   return bt->B <= bt->ctx->coop_max_batch && bt->nfac >= 1536; /* measured (ms per solve, coop / one workgroup): n = 384 14.0 / 11.7, 512 20.5 / 21.2, 768 28.6 / 39.0, 1000 40.6 / 64.0,
                                             2500 137 / 1712, 5000 399 / ~7000 */
 }
+/* sparse coop mode: decided at setup, where the launch plans are made (sparse_setup) */
+static bool sparse_coop_wanted(const qpg_batch *bt) { return bt->sparse && !bt->kkt && !bt->sp_plan.empty(); }
 /* runs one launch chain: plainly the first time (function attributes get set), recorded into a graph the second time, replayed after */
 template <class F> static void co_chain(qpg_batch *bt, int key, F issue) {
   if (!RT_GRAPHS || !bt->ctx->coop_graphs || key < 0) { issue(); return; }
@@ -1187,6 +1255,31 @@ template <class F> static void co_chain(qpg_batch *bt, int key, F issue) {
   RT_GRAPH_LAUNCH(g.exec);
 }
 static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qpg_scalars &sc) {
+  if (bt->sparse) { /* sparse coop mode: the member's plan, launch by launch (chains 0 / 1: the factorisation into the factor / LD_Q, 2: the solve) */
+    const qpg_batch::SpPlan &P = bt->sp_plan[(size_t)b];
+    const int slot = b;
+    {
+      char sig[200];
+      snprintf(sig, sizeof(sig), "sp %d %d %p %p %p %p", V.sp_co_G, (int)bt->lds_bytes, (void *)bt->sparse_d, (void *)V.LQ, (void *)V.sc, (void *)V.sp_co_wv);
+      if (bt->co_sig != sig) { co_graphs_clear(bt); bt->co_sig = sig; }
+    }
+    if (sc.pend_la == 1 || sc.pend_la == 3 || sc.pend_la == 7) { /* (with or without A' Sigma A, the proximal term, gamma: read from the QP's scalars by the kernel) */
+      const int which = (sc.pend_la == 7) ? 1 : 0;
+      co_chain(bt, b * 16 + which, [&]() {
+        for (const auto &l : P.factor) RT_LAUNCH(QP_INST(qp512, k_co_sp_factor), l.grid, QP_T, (size_t)bt->lds_bytes, V, b, slot, which, l.lev0, l.lev1);
+      });
+    }
+    if (sc.pend_kind == 0 && sc.pend_la != 7) { /* Newton step: d = -(L D L')^{-1} dphi */
+      co_chain(bt, b * 16 + 2, [&]() {
+        RT_LAUNCH(QP_INST(qp512, k_co_sp_solve), P.vec_grid, QP_T, (size_t)64, V, b, slot, 0, 0, 0);
+        for (const auto &l : P.solve) RT_LAUNCH(QP_INST(qp512, k_co_sp_solve), l.grid, QP_T, (size_t)64, V, b, slot, 1, l.lev0, l.lev1);
+        RT_LAUNCH(QP_INST(qp512, k_co_sp_solve), P.vec_grid, QP_T, (size_t)64, V, b, slot, 2, 0, 0);
+        for (size_t k = P.solve.size(); k-- > 0;) RT_LAUNCH(QP_INST(qp512, k_co_sp_solve), P.solve[k].grid, QP_T, (size_t)64, V, b, slot, 3, P.solve[k].lev0, P.solve[k].lev1);
+        if (!P.solve.empty() && P.solve[0].grid > 1) RT_LAUNCH(QP_INST(qp512, k_co_sp_solve), P.vec_grid, QP_T, (size_t)64, V, b, slot, 3, 0, 0);
+      });
+    }
+    return 0;
+  }
   const int n = bt->probs[b].n, NB = 32, slot = b;
   const int G = std::max(8, std::min(bt->ctx->coop_workgroups, 1024 / std::max(1, bt->B))); /* the members' chains run side by side (coop_solve) */
   /* FactorLds + FactorStage / SolveLds: below 48 KB, so that no launch needs a function-attribute call */
@@ -1240,12 +1333,13 @@ static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qp
 static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V, int budget, int dynamic, float *ms);
 static int coop_solve(qpg_batch *bt) {
   qpg_view V = bt->V;
-  V.offload = bt->ctx->coop_updates ? 2 : 1;
+  V.offload = bt->sparse ? 1 : (bt->ctx->coop_updates ? 2 : 1); /* sparse coop mode: path updates stay on the QP's workgroup, and so does the one-workgroup path's refactorise-or-update rule */
   /* refactorise-or-update: an update_rank_threshold the user set explicitly wins; else coop_rank_threshold (-2: by measured cost) */
+  if (!bt->sparse)
   V.update_rank_threshold = (bt->ctx->update_rank_threshold >= 0) ? bt->ctx->update_rank_threshold
                             : ((bt->ctx->coop_rank_threshold == -2) ? 16 * (bt->nfac / 2048) : bt->ctx->coop_rank_threshold);
   V.co_tab = nullptr; V.co_flags = nullptr; V.co_tab_stride = 0;
-  if (bt->ctx->coop_updates == 2) { /* tables + counter words of the persistent sweep, per member */
+  if (!bt->sparse && bt->ctx->coop_updates == 2) { /* tables + counter words of the persistent sweep, per member */
     const size_t stride = ((size_t)bt->nfac / 32 + 2) * CO_UD_TAB(QPG_KMAX), flag_bytes = align_up((size_t)bt->B * 4 * sizeof(int), 256);
     if (!bt->co_tab_d) {
       if (RT_MALLOC(&bt->co_tab_d, flag_bytes + (size_t)bt->B * stride * sizeof(double)) != 0) { bt->co_tab_d = nullptr; return fail(QPG_ERR_ALLOC, "device allocation failed (coop update tables)"); }
@@ -1330,7 +1424,7 @@ extern "C" int qpg_batch_begin_solve(qpg_batch *bt) {
 extern "C" int qpg_batch_solve(qpg_batch *bt) {
   NEED_SETUP(bt, "qpg_batch_solve");
   std::fill(bt->host_status.begin(), bt->host_status.end(), QPG_UNSOLVED); /* an error mark of an earlier update_* call ends here, as in the reference */
-  if (coop_wanted(bt)) return coop_solve(bt);
+  if (coop_wanted(bt) || sparse_coop_wanted(bt)) return coop_solve(bt);
   return launch_solve(bt, 0x7fffffff, (bt->B > bt->nslots ? 1 : 0) | 2); /* finished QPs are re-armed on the device */
 }
 

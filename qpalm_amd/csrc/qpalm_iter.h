@@ -341,8 +341,8 @@ QPP int dev_update_sigma_pre(const qpg_view &V, const QpArrays &a, IterShared &I
   if (tid == 0) { I.s.nb_sigma_changed = nchg; I.s.n_sigma_updates++; }
   __syncthreads();
   double thr = qmin(st.max_rank_update_fraction * (double)(n + m), 0.25 * (double)st.max_rank_update);
-  if (V.offload && V.update_rank_threshold >= 0) thr = qmin(thr, (double)V.update_rank_threshold); /* coop mode: beyond its threshold the factor is rebuilt by many workgroups
-                                                                        instead of updated by one (speed policy, same matrix) */
+  if (V.offload && !V.sparse && V.update_rank_threshold >= 0) thr = qmin(thr, (double)V.update_rank_threshold); /* coop mode: beyond its threshold the factor is rebuilt by many workgroups
+                                                                        instead of updated by one (speed policy, same matrix; sparse coop mode keeps the one-workgroup rule) */
   int nupd = 0;
   if (V.kkt) {
     /* FACTORIZE_KKT (iteration.c:135-144, solver_interface.c:463-481): every branch that changes anything ends in
@@ -1006,6 +1006,9 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
     }
     } /* !dual_init */
     QP_OPAQUE(a.b);
+    if constexpr (SPARSE) { /* a chain-like tree: refactorising is cheaper than walking it per row (decided ahead of the suspension: sparse coop mode offloads that refactorisation too) */
+      if (!resume && la == 2 && !sp_update_pays(nchange, V.sp_nlev[b], n)) { la = 1; action = 1; }
+    }
     if (V.offload && !resume && !V.kkt && (la == 1 || la == 3 || la == 7 || (kind == QP_KIND_NEWTON && la == 0) || (V.offload >= 2 && (la == 2 || la == 4)))) {
       /* coop mode: hand the factorisation or the rank update (and the Newton solve that follows it) to the host's multi-workgroup
        * kernels.  With offload == 1 the rank updates (la == 2, 4) stay on this workgroup and only the solve after them goes to the host */
@@ -1027,8 +1030,25 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
        * paths where that pays, a refactorisation otherwise; changed penalties likewise (la == 4: ldlupdate_sigma_changed as path updates with the scaled
        * rows, dev_update_sigma_pre decides) */
       const SpArrays SP = sp_arrays(V, b, slot, Dg, lds);
-      if (la == 2 && !sp_update_pays(nchange, SP.nlev, n)) { la = 1; action = 1; } /* a chain-like tree: refactorising is cheaper than walking it per row */
-      if (la == 2) sp_updown(V, b, n, SP, a.enter(), I.s.nb_enter, a.leave(), I.s.nb_leave);
+      if (resume) { /* sparse coop mode: the host's kernels have factorised (k_co_sp_factor) and / or solved (k_co_sp_solve) */
+        if (la == 7) { /* LD_Q is ready (qpalm.c:459-468) */
+          SpArrays SQ = SP; SQ.Lx = LQ; SQ.Dg = DgQ;
+          const double dobj = dev_dual_objective_sp(V, a, b, SQ, I);
+          if (tid == 0) { I.s.dual_objective = dobj; I.s.dual_pending = 0; }
+          __syncthreads();
+          continue;
+        }
+      } else
+      if (la == 2) {
+        sp_updown(V, b, n, SP, a.enter(), I.s.nb_enter, a.leave(), I.s.nb_leave);
+        if (V.offload && kind == QP_KIND_NEWTON) { /* sparse coop mode: the path updates stay here, the solve with the updated factor goes to the host */
+          for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1;
+          __syncthreads();
+          if (tid == 0) { I.s.pend_stage = 1; I.s.pend_la = 0; I.s.pend_action = action; I.s.pend_kind = kind; I.s.pend_nchange = nchange; I.s.pend_gam = gam; }
+          __syncthreads();
+          break;
+        }
+      }
       else if (la == 4) sp_updown(V, b, n, SP, a.enter(), n_sig, a.leave(), 0); /* ldlupdate_sigma_changed: the rows listed in enter[], scaled by dev_ldlupdate_sigma_scale */
       else if (la == 1 || la == 3) sp_factor(V, b, n, SP, la == 1, prox != 0, gam);
       else if (la == 5) gersh_ub = sp_gershgorin(V, b, n, SP, I.S);
@@ -1091,7 +1111,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
     if (kind == QP_KIND_NEWTON) {
       /* ldlsolveLD_neg_dphi (solver_interface.c:505-519) */
       if constexpr (SPARSE) {
-        if (!V.kkt) { /* (KKT mode: spk_newton has solved) */
+        if (!V.kkt && !resume) { /* (KKT mode: spk_newton has solved; sparse coop mode: the host's kernels have) */
           for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1;
           sp_solve(n, sp_arrays(V, b, slot, Dg, lds), a.d());
         }
@@ -1111,7 +1131,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
         if (action == 3) { I.s.n_factor_Q++; I.s.ticks_factor += t1 - t0; }
         if (action == 2) { if (!V.kkt) I.s.n_rank1 += nchange; I.s.n_sweeps = (int)I.s.ticks_dbg[QPG_CNT_SWEEPS]; I.s.ticks_update += t1 - t0; }
         I.s.n_solve++; I.s.ticks_solve += t2 - t1;
-        if (!V.kkt && (RPT > 0) && !QP_NOFUSE && action == 2 && !V.offload) I.s.n_fused_solve++;
+        if (!V.kkt && (RPT > 0) && !QP_NOFUSE && action == 2 && (SPARSE || !V.offload)) I.s.n_fused_solve++;
         I.s.last_fact = action;
       }
       QP_OPAQUE(a.b);

@@ -654,6 +654,27 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_co_solve(qpg_view V, int 
   else { for (int i = blockIdx.x * QP_T + threadIdx.x; i < n; i += QP_T * gridDim.x) a.d()[i] = a.temp_n()[i]; }
 }
 
+/* ---- sparse coop mode (context option "sparse_coop"; qpalm_capi.inc: sparse_coop_plan): the sparse L D L' of ONE QP on many workgroups.  The launch
+ * plan cuts the levels of the elimination tree into launches: a level wider than one workgroup's round is a launch of its own on a grid (its columns /
+ * rows grid-strided), a run of narrower levels one launch on one workgroup.  What differs between two calls of a recorded chain is read from the QP's
+ * scalars (pend_la: with or without A' Sigma A; the proximal term; pend_gam), not passed as an argument. ---- */
+/* assembly + factorisation of the levels [lev0, lev1); which = 0: the factor of the Newton system, 1: LD_Q of the dual objective (pend_la == 7) */
+__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_co_sp_factor(qpg_view V, int b, int slot, int which, int lev0, int lev1) {
+  char *lds = QP_DYN_LDS();
+  if ((int)blockIdx.x >= V.sp_co_G) return; /* (a workgroup without work vectors of its own: the plan never asks for one) */
+  const qpg_scalars &sc = V.sc[b];
+  const int la = sc.pend_la, prox = qp_prox(*V.settings, sc), ngrp = QP_NW * V.sp_gpw;
+  SpArrays S = sp_arrays(V, b, slot, (which ? V.DgQ : V.Dg) + (size_t)slot * V.nfac, lds);
+  if (which) S.Lx = V.LQ + (size_t)slot * V.sp_nnzL;
+  S.wv = V.sp_co_wv + ((size_t)b * V.sp_co_G + blockIdx.x) * ngrp * V.nfac;
+  sp_factor(V, b, qp_arrays(V, b).n, S, la == 1, la != 7 && prox != 0, sc.pend_gam, 0, lev0, lev1, (int)blockIdx.x * ngrp, (int)gridDim.x * ngrp);
+}
+/* ldlsolveLD_neg_dphi on d (the suspended iteration wrote -dphi there); the phases: sp_co_solve (qpalm_sparse.h) */
+__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_co_sp_solve(qpg_view V, int b, int slot, int phase, int lev0, int lev1) {
+  const QpArrays a = qp_arrays(V, b);
+  sp_co_solve(a.n, sp_arrays(V, b, slot, V.Dg + (size_t)slot * V.nfac, QP_DYN_LDS()), a.d(), phase, lev0, lev1);
+}
+
 /* ldlupdate_entering_constraints / ldldowndate_leaving_constraints / ldlupdate_sigma_changed (solver_interface.c:407-503) of a
  * suspended iteration, sweep r0 / 16 over ranks r0 .. r0 + 15 of the list (entering rows first, then leaving rows; the counts are
  * read from the QP's scalars, so that the launch chain of a sweep is the same every time and can be replayed as a graph):

@@ -24,7 +24,9 @@
  *    the tree is bushy enough for that to be cheaper than a refactorisation (sp_update_pays), else a refactorisation.  Changes of
  *    sigma refactorise (the reference's own behaviour under FACTORIZE_KKT, iteration.c:135-144).
  * One workgroup per QP like the dense engine: batches of sparse QPs fill the chip; a single large sparse QP runs at the latency of
- * its level chain (a band matrix has n levels).  DESIGN.md section 2.
+ * its level chain (a band matrix has n levels) -- or, context option "sparse_coop", its factorisations and Newton solves run level by level
+ * on many workgroups (k_co_sp_factor / k_co_sp_solve in qpalm_kernels.h call the functions below with a range of levels and the
+ * workgroup's place in the grid; path updates stay on the QP's workgroup).  DESIGN.md section 2.
  */
 #ifndef QPALM_SPARSE_H
 #define QPALM_SPARSE_H
@@ -77,11 +79,14 @@ QPD bool sp_level_needs_barrier(const SpArrays &S, int lev) {
 }
 /* H = Q (+ A' Sigma_act A) (+ I / gamma) assembled column by column and factorised in the same pass (see the header).
  * with_AtSA = false, proximal = false: the second resident factor LD_Q of the dual objective (dev_solve, la == 7), into the value arrays the caller points S at.
+ * The levels [lev0, lev1) of the elimination tree (lev1 < 0: all of them), this workgroup's groups being groups g0 .. g0 + ngrp - 1 of gtot (gtot = 0: the
+ * workgroup alone).  Sparse coop mode (k_co_sp_factor) launches a wide level on many workgroups -- a column's arithmetic does not depend on the group that
+ * computes it, and the kernel boundary is the level's barrier -- and a run of narrow levels on one: the same code either way.
  * KKT = true (qpalm_sparse_kkt.h; with_AtSA = false): K = [[Q + I / gamma, A_a'], [A_a, -Sigma_a^-1]] of n = nv + m rows instead -- a variable's column
  * (perm[j] < nv) takes Q, 1 / gamma and A's entries toward the constraints with kkt_state 1; such a constraint's column (non-empty: a constraint
  * with an entry) its row of A and -1 / sigma; any other constraint's column a unit diagonal.  The updates and the pivots are the same code. */
 template <bool KKT = false>
-QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma, int nv = 0) {
+QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma, int nv = 0, int lev0 = 0, int lev1 = -1, int g0 = 0, int gtot = 0) {
   /* a column per GROUP of lanes: the columns of a sparse factor are short (a band: half a dozen entries), so a wavefront takes gpw = 1, 2,
    * 4 or 8 columns of the level at a time (8 lanes each at 8) and a 512-thread workgroup up to 64 -- every step of a column is a chain of
    * dependent HBM round trips, the groups' chains overlap.  Loops run to the wavefront's longest trip count with the other groups
@@ -124,10 +129,12 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
   double QP_LDS_AS *wl = QP_LDS_ARG(double, S.lds) + (size_t)grp * cap_lds;
   int QP_LDS_AS *ridx = (int QP_LDS_AS *)(QP_LDS_ARG(double, S.lds) + (size_t)ngrp * cap_lds) + (size_t)grp * cap_lds;
   const int gbase = lane & ~(spg - 1);
+  if (lev1 < 0) lev1 = S.nlev;
+  if (gtot <= 0) gtot = ngrp;
   __syncthreads();
-  for (int lev = 0; lev < S.nlev; lev++) {
+  for (int lev = lev0; lev < lev1; lev++) {
     const int c0 = S.levptr[lev], c1 = S.levptr[lev + 1];
-    for (int cw = c0 + wid * gpw; cw < c1; cw += ngrp) { /* (the same for the lanes of a wavefront) */
+    for (int cw = c0 + g0 + wid * gpw; cw < c1; cw += gtot) { /* (the same for the lanes of a wavefront) */
       const int c = cw + lane / spg;
       const bool on = c < c1;
       const int j = on ? S.levcol[c] : 0;
@@ -511,48 +518,57 @@ QPNI void sp_updown(const qpg_view &V, int b, const int n, const SpArrays &S_, c
 #ifndef QP_SPU
 #define QP_SPU 4
 #endif
-template <class XP> QPD void sp_solve_levels(const int n, const SpArrays &S, XP x) {
-  for (int lev = 0; lev < S.nlev; lev++) { /* forward: a row needs the rows of its structure, which sit in earlier levels */
-    for (int c = S.levptr[lev] + (int)threadIdx.x; c < S.levptr[lev + 1]; c += QP_T) {
-      const int j = S.levcol[c];
-      double v = x[j];
-      int r = S.Rp[j];
-      const int r1 = S.Rp[j + 1];
-      for (; r + QP_SPU <= r1; r += QP_SPU) {
-        int pp[QP_SPU], kk[QP_SPU];
-        double lv[QP_SPU];
+/* one level of the forward solve (a row needs the rows of its structure, which sit in earlier levels) / of the backward solve (a column needs the
+ * rows of its pattern: ancestors, later levels): this thread is thread t0 of ttot over the level's rows -- the workgroup's own (threadIdx.x of QP_T) or a
+ * grid's (sparse coop mode, sp_co_solve) */
+template <class XP> QPD void sp_forward_level(const SpArrays &S, XP x, const int lev, const int t0, const int ttot) {
+  for (int c = S.levptr[lev] + t0; c < S.levptr[lev + 1]; c += ttot) {
+    const int j = S.levcol[c];
+    double v = x[j];
+    int r = S.Rp[j];
+    const int r1 = S.Rp[j + 1];
+    for (; r + QP_SPU <= r1; r += QP_SPU) {
+      int pp[QP_SPU], kk[QP_SPU];
+      double lv[QP_SPU];
 #pragma unroll
-        for (int u = 0; u < QP_SPU; u++) { pp[u] = S.Rpos[r + u]; kk[u] = S.Rk[r + u]; }
+      for (int u = 0; u < QP_SPU; u++) { pp[u] = S.Rpos[r + u]; kk[u] = S.Rk[r + u]; }
 #pragma unroll
-        for (int u = 0; u < QP_SPU; u++) lv[u] = S.Lx[pp[u]];
+      for (int u = 0; u < QP_SPU; u++) lv[u] = S.Lx[pp[u]];
 #pragma unroll
-        for (int u = 0; u < QP_SPU; u++) v -= lv[u] * x[kk[u]];
-      }
-      for (; r < r1; r++) v -= S.Lx[S.Rpos[r]] * x[S.Rk[r]];
-      x[j] = v;
+      for (int u = 0; u < QP_SPU; u++) v -= lv[u] * x[kk[u]];
     }
+    for (; r < r1; r++) v -= S.Lx[S.Rpos[r]] * x[S.Rk[r]];
+    x[j] = v;
+  }
+}
+template <class XP> QPD void sp_backward_level(const SpArrays &S, XP x, const int lev, const int t0, const int ttot) {
+  for (int c = S.levptr[lev] + t0; c < S.levptr[lev + 1]; c += ttot) {
+    const int j = S.levcol[c];
+    double v = x[j];
+    int e = S.Lp[j];
+    const int e1 = S.Lp[j + 1];
+    for (; e + QP_SPU <= e1; e += QP_SPU) {
+      int ii[QP_SPU];
+      double lv[QP_SPU];
+#pragma unroll
+      for (int u = 0; u < QP_SPU; u++) { ii[u] = S.Li[e + u]; lv[u] = S.Lx[e + u]; }
+#pragma unroll
+      for (int u = 0; u < QP_SPU; u++) v -= lv[u] * x[ii[u]];
+    }
+    for (; e < e1; e++) v -= S.Lx[e] * x[S.Li[e]];
+    x[j] = v;
+  }
+}
+template <class XP> QPD void sp_solve_levels(const int n, const SpArrays &S, XP x) {
+  for (int lev = 0; lev < S.nlev; lev++) {
+    sp_forward_level(S, x, lev, (int)threadIdx.x, QP_T);
     if (sp_level_needs_barrier(S, lev)) __syncthreads();
   }
   __syncthreads();
   for (int j = threadIdx.x; j < n; j += QP_T) x[j] = x[j] / S.Dg[j];
   __syncthreads();
-  for (int lev = S.nlev - 1; lev >= 0; lev--) { /* backward: a column needs the rows of its pattern (ancestors: later levels) */
-    for (int c = S.levptr[lev] + (int)threadIdx.x; c < S.levptr[lev + 1]; c += QP_T) {
-      const int j = S.levcol[c];
-      double v = x[j];
-      int e = S.Lp[j];
-      const int e1 = S.Lp[j + 1];
-      for (; e + QP_SPU <= e1; e += QP_SPU) {
-        int ii[QP_SPU];
-        double lv[QP_SPU];
-#pragma unroll
-        for (int u = 0; u < QP_SPU; u++) { ii[u] = S.Li[e + u]; lv[u] = S.Lx[e + u]; }
-#pragma unroll
-        for (int u = 0; u < QP_SPU; u++) v -= lv[u] * x[ii[u]];
-      }
-      for (; e < e1; e++) v -= S.Lx[e] * x[S.Li[e]];
-      x[j] = v;
-    }
+  for (int lev = S.nlev - 1; lev >= 0; lev--) {
+    sp_backward_level(S, x, lev, (int)threadIdx.x, QP_T);
     if (lev == 0 || sp_level_needs_barrier(S, lev - 1)) __syncthreads();
   }
   __syncthreads();
@@ -579,6 +595,39 @@ QPNI void sp_solve(const int n, const SpArrays &S_, double *xo) {
     for (int j = threadIdx.x; j < n; j += QP_T) xo[S.perm[j]] = x[j];
   }
   __syncthreads();
+}
+
+/* Sparse coop mode (k_co_sp_solve): the same solve as a chain of launches on a grid of workgroups, the right-hand side in HBM (S.tmp) because several
+ * workgroups share it.  phase 0: x <- P b; 1: the forward levels [lev0, lev1); 2: x <- D^-1 x; 3: the backward levels lev1 - 1 .. lev0 and, in the launch
+ * that ends the chain (level 0 done by this workgroup alone, or no level at all), b <- P' x.  A launch of more than one level runs on ONE workgroup, with the
+ * barriers of sp_solve_levels; a level of its own may run on many, the kernel boundary being its barrier. */
+QPNI void sp_co_solve(const int n, const SpArrays &S_, double *xo, const int phase, const int lev0, const int lev1) {
+#if QP_SP_LOCAL
+  const SpArrays S = S_;
+#else
+  const SpArrays &S = S_;
+#endif
+  double *x = S.tmp;
+  const int t0 = (int)blockIdx.x * QP_T + (int)threadIdx.x, ttot = (int)gridDim.x * QP_T;
+  if (phase == 0) {
+    for (int j = t0; j < n; j += ttot) x[j] = xo[S.perm[j]];
+  } else if (phase == 1) {
+    for (int lev = lev0; lev < lev1; lev++) {
+      sp_forward_level(S, x, lev, t0, ttot);
+      if (lev + 1 < lev1 && sp_level_needs_barrier(S, lev)) __syncthreads();
+    }
+  } else if (phase == 2) {
+    for (int j = t0; j < n; j += ttot) x[j] = x[j] / S.Dg[j];
+  } else {
+    for (int lev = lev1 - 1; lev >= lev0; lev--) {
+      sp_backward_level(S, x, lev, t0, ttot);
+      if (lev > lev0 && sp_level_needs_barrier(S, lev - 1)) __syncthreads();
+    }
+    if (lev0 == 0 && (gridDim.x == 1 || lev1 == 0)) {
+      __syncthreads();
+      for (int j = t0; j < n; j += ttot) xo[S.perm[j]] = x[j];
+    }
+  }
 }
 
 #endif

@@ -91,7 +91,7 @@ typedef struct {
 /* view of one batch in device memory; passed by value to the kernels */
 typedef struct {
   int32_t B, n, m, ld, nnzA, nnzQ, nnzQf, nslots, lds_bytes, update_rank_threshold, ls_stride, wst_stride, place_panel_wave, narrow_rows;
-  int32_t offload, sweep_ranks; /* sweep_ranks: most ranks one sweep of the rank update applies (16, the default, or 32 = the multi-pass form of dense_updown: bit-identical factors, measured slower).  coop mode: 1 = dev_solve suspends at its linear-algebra site for factorisations and Newton solves, 2 = for rank updates too */
+  int32_t offload, sweep_ranks; /* sweep_ranks: most ranks one sweep of the rank update applies (16, the default, or 32 = the multi-pass form of dense_updown: bit-identical factors, measured slower).  coop mode: 1 = dev_solve suspends at its linear-algebra site for factorisations and Newton solves (sparse coop mode: always 1, path updates stay on the workgroup), 2 = for rank updates too */
   int32_t kkt_compact, kkt_pad; /* 1: KKT mode factorises the variables + ACTIVE constraints only and spreads the factor out (qpalm_kkt.h) */
   int32_t kkt, nfac; /* kkt != 0: FACTORIZE_KKT, the factor slots hold the (n+m) x (n+m) KKT panel; nfac = rows of a factor slot
                         (n, or n + m in KKT mode); ld = its leading dimension */
@@ -141,6 +141,8 @@ typedef struct {
   int32_t ls_hbm;           /* tests: >= 1 = the line search keeps its sort buffer in HBM (the LDS-tiled sort) whatever m; >= 2: tiles of at most that many entries */
   int32_t sp_lds;           /* context option "sparse_lds" (default 1): columns are accumulated, and right-hand sides solved, in LDS where they fit (0: the HBM forms) */
   int32_t sp_gpw;           /* columns a wavefront factorises at a time (1, 2, 4 or 8 groups of 64 / sp_gpw lanes): sp_wv holds wavefronts x sp_gpw work vectors per slot */
+  int32_t sp_co_G;          /* sparse coop mode (context option "sparse_coop"): most workgroups of one launch of k_co_sp_factor; 0 = the batch runs on one workgroup per QP */
+  double *sp_co_wv;         /* [B][sp_co_G][wavefronts x sp_gpw][n] the work vectors of those workgroups (zero outside of use); NULL without sparse coop mode */
   qpg_scalars *sc; /* [B] */
   qpg_settings *settings; /* [1] */
   int32_t *queue; /* [64 + QPG_CU_KEYS]: [0] work-queue head; [64 + key] workgroups that have arrived on compute unit `key` in this launch */

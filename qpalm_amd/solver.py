@@ -167,6 +167,13 @@ class QpalmBatch:
         self._check(self.L.qpg_batch_sparse_perm(self.h, int(b), perm.ctypes.data_as(C.POINTER(capi.c_int)), C.byref(lev)))
         return perm, int(lev.value)
 
+    def sparse_coop_info(self, b=0):
+        """(factor_launches, solve_launches, max_grid): member b's launch plan under the context option "sparse_coop" = 1; (0, 0, 0) when the batch runs
+        on one workgroup per QP; raises on a batch with dense factors"""
+        f, s, g = capi.c_int(0), capi.c_int(0), capi.c_int(0)
+        self._check(self.L.qpg_batch_sparse_coop_info(self.h, int(b), C.byref(f), C.byref(s), C.byref(g)))
+        return int(f.value), int(s.value), int(g.value)
+
     def num_unfinished(self):
         c = capi.c_int(0)
         self._check(self.L.qpg_batch_num_unfinished(self.h, C.byref(c)))
