@@ -1290,13 +1290,14 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
     } else jmin = (pre_jmin < n) ? pre_jmin : n - 1;
     if (fuse) jmin = 0;
     jmin = QP_UNIFORM(block_imin(S, jmin)); /* same value in every lane: keep the block loops scalar */
-    /* lane r of every 16-lane row of the panel wave carries alpha_r and 1/alpha_r of rank 16 g + r (QP_RECUR_DPP; else lane r, G = 1);
-     * they run on through the passes */
-    double alpha[G], ialpha[G], sg[G];
+    /* lane r of every 16-lane row of the panel wave carries 1/alpha_r of rank 16 g + r (QP_RECUR_DPP; else lane r, G = 1); it runs on
+     * through the passes.  (alpha_r itself, and with it the reciprocal of the pivot before the rank, is needed by nothing here: p and
+     * gamma take 1/alpha only, so the column pays for ONE reciprocal per rank group.) */
+    double ialpha[G], sg[G];
     const int rl = QP_RECUR_DPP ? (lane & 15) : lane;
 #pragma unroll
     for (int g = 0; g < G; g++) {
-      alpha[g] = 1.0; ialpha[g] = 1.0;
+      ialpha[g] = 1.0;
       sg[g] = (16 * g + rl < kk) ? ((r0 + 16 * g + rl < n_up) ? 1.0 : -1.0) : 0.0;
     }
     const int J0 = (jmin / NB) * NB;
@@ -1611,114 +1612,126 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
          * long-lived values that spill under the 128-VGPR cap, and every column then waits on
          * ~5 dependent scratch loads (measured: 1830 clk/column vs ~900 for this form). */
         double QP_LDS_AS *const wt = QP_LDS_VBASE(&U.Wt[0]);
+        /* Fused solve: the block's part of the forward substitution, y_J = L_JJ^{-1} (b_J - contributions of the earlier blocks), rides in
+         * this loop.  Column c1 of the block is final once its last rank is in and lane c1 of v once the columns before c1 are, so
+         * v -= l y_c1 follows the column's FMAs: per row the same FMAs in the same ascending order as a loop of its own behind this
+         * one, without its 32 dependent LDS round trips.  Rows that take no part multiply by 0.0 as there (not skipped: -0.0 and a
+         * non-finite y keep their bits).  Two instances of the loop: the unfused sweep pays nothing for it.
+         * Not in the 32-rank form (FOLD): its column loop holds 32 running values per lane and has no register to spare -- with the
+         * substitution inside, and already with a second instance of the loop, the compiler spills inside the loop (measured: the
+         * 32-rank benchmark run 1670 -> 2350 ms).  There the substitution stays a loop of its own behind this one. */
+        constexpr bool FOLD = (K <= 16);
+        double vsub = accp;
+        auto recurrence = [&](auto fused_solve) QP_ALWAYS_INLINE {
+          constexpr bool FS = decltype(fused_solve)::value;
 #pragma unroll 1
-        for (int c1 = 0; c1 < jb; c1++) {
-          const int ln = QP_FRESH_LANE(lane);
-          const double lcur = lnext;
-          lnext = (ln > c1 + 1 && ln < jb) ? U.Ld[cur][ln][c1 + 1] : 0.0; /* in flight during this column (column NB is padding) */
-          /* QP_PANEL_TIMING == 2 (diagnostic build): ms_dbg[8..11] = the column's four links: pivot row through LDS to lane = rank /
-           * rank scalars / table entry through LDS back to every lane / the 2 K FMAs (each stamp drains the LDS queue first) */
-          long long tc0 = 0;
-          if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); tc0 = QP_CLOCK(); }
-          if (ln == c1) {
+          for (int c1 = 0; c1 < jb; c1++) {
+            const int ln = QP_FRESH_LANE(lane);
+            const double lcur = lnext;
+            lnext = (ln > c1 + 1 && ln < jb) ? U.Ld[cur][ln][c1 + 1] : 0.0; /* in flight during this column (column NB is padding) */
+            /* QP_PANEL_TIMING == 2 (diagnostic build): ms_dbg[8..11] = the column's four links: pivot row through LDS to lane = rank /
+             * rank scalars / table entry through LDS back to every lane / the 2 K FMAs (each stamp drains the LDS queue first) */
+            long long tc0 = 0;
+            if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); tc0 = QP_CLOCK(); }
+            if (ln == c1) {
 #pragma unroll
-            for (int r = 0; r < K; r++) wt[r] = wrow[r];
-          }
-          QP_WAVE_SYNC();
-          /* rank-indexed scalars: lane = rank within its group (lanes >= kk carry w = 0 => gamma = 0: exact no-ops).  The groups of
-           * 16 ranks follow each other in the same lanes; group g starts from the pivot group g-1 leaves. */
-          const int rk = QP_RECUR_DPP ? (ln & 15) : ln;
-          double d0 = qp_readlane(dreg, c1);
-          double nwv[G], ngam[G];
-#pragma unroll
-          for (int g = 0; g < G; g++) {
-            const int kkg = (kk - 16 * g < KG) ? (kk - 16 * g) : KG; /* ranks of this group in this sweep (wave-uniform; <= 0: none) */
-            nwv[g] = 0.0; ngam[g] = 0.0;
-            if (g > 0 && kkg <= 0) continue;
-            const double wv = (rk < kkg) ? wt[(16 * g + rk) & (K - 1)] : 0.0;
-            if (QP_PANEL_TIMING == 2 && g == 0) { QP_DRAIN_LDS(); const long long t = QP_CLOCK(); if (lane == 0) tdbg[8] += t - tc0; tc0 = t; }
-            const double p = sg[g] * wv * wv * ialpha[g];
-            double dnew, dprev;
-            if (qp_rank_pivots<KG>(p, ln, d0, pivmode, dnew, dprev) && lane == 0) tdbg[QPG_CNT_SEQ_COLS] += 1; /* (rare: the guard re-summed this column) */
-            const double rdn = qp_rcp(dnew), rdp = qp_rcp(dprev);
-            const double gam = -sg[g] * wv * ialpha[g] * rdn;
-            if (ln < KG) { QP_CWG(U, cur, c1)[16 * g + ln][0] = -wv; QP_CWG(U, cur, c1)[16 * g + ln][1] = -gam; } /* stored negated: plain FMAs below */
-            /* a rank whose vector is zero in this column leaves its alpha alone: d_new / d_prev is exactly 1 there, d * rcp(d) is not.
-             * (Columns above a rank's first nonzero are then exact no-ops: the result does not depend on where a sweep starts or on
-             * how the ranks are grouped into sweeps.) */
-            alpha[g] = (wv == 0.0) ? alpha[g] : alpha[g] * dnew * rdp;
-            ialpha[g] = (wv == 0.0) ? ialpha[g] : ialpha[g] * dprev * rdn;
-            d0 = qp_readlane(dnew, kkg - 1); /* pivot of the column after this group's last rank */
-            nwv[g] = -wv; ngam[g] = -gam;
-          }
-          if (QP_PANEL_TIMING == 2) { double gg = ngam[0]; QP_OPAQUE_V(gg); const long long t = QP_CLOCK(); if (lane == 0) tdbg[9] += t - tc0; tc0 = t; }
-          if (ln == c1) dreg = d0; /* final pivot of the column = value after the last rank */
-          if (!QP_RECUR_DPP) QP_WAVE_SYNC();
-          /* rows of the block: lane = row.  Rows <= c1 are finished, their registers may be
-           * overwritten freely, so no selects: w_r -= w_j l ; l -= gamma w_r  (2 FMAs per rank) */
-          if (QP_RECUR_DPP) {
-            double l = lcur;
-            qp_apply_ranks_dpp<K, 0, 0, 8>(nwv[0], ngam[0], wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
-            if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16, false>(nwv[0], ngam[0], wrow, l);
-            if constexpr (G > 1) {
-              if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(nwv[1], ngam[1], wrow, l);
-              if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16, false>(nwv[1], ngam[1], wrow, l);
+              for (int r = 0; r < K; r++) wt[r] = wrow[r];
             }
-            if (ln > c1 && ln < jb) U.Ld[cur][ln][c1] = l;
-            if (QP_PANEL_TIMING == 2) { double ll = l; QP_OPAQUE_V(ll); const long long t = QP_CLOCK(); if (lane == 0) tdbg[11] += t - tc0; }
-          } else {
-            static_assert(QP_RECUR_DPP || G == 1, "the LDS form of the recurrence handles one rank group");
+            QP_WAVE_SYNC();
+            /* rank-indexed scalars: lane = rank within its group (lanes >= kk carry w = 0 => gamma = 0: exact no-ops).  The groups of
+             * 16 ranks follow each other in the same lanes; group g starts from the pivot group g-1 leaves. */
+            const int rk = QP_RECUR_DPP ? (ln & 15) : ln;
+            double d0 = qp_readlane(dreg, c1);
+            double nwv[G], ngam[G];
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+              const int kkg = (kk - 16 * g < KG) ? (kk - 16 * g) : KG; /* ranks of this group in this sweep (wave-uniform; <= 0: none) */
+              nwv[g] = 0.0; ngam[g] = 0.0;
+              if (g > 0 && kkg <= 0) continue;
+              const double wv = (rk < kkg) ? wt[(16 * g + rk) & (K - 1)] : 0.0;
+              if (QP_PANEL_TIMING == 2 && g == 0) { QP_DRAIN_LDS(); const long long t = QP_CLOCK(); if (lane == 0) tdbg[8] += t - tc0; tc0 = t; }
+              const double p = sg[g] * wv * wv * ialpha[g];
+              double dnew, dprev;
+              if (qp_rank_pivots<KG>(p, ln, d0, pivmode, dnew, dprev) && lane == 0) tdbg[QPG_CNT_SEQ_COLS] += 1; /* (rare: the guard re-summed this column) */
+              const double rdn = qp_rcp(dnew);
+              const double gam = -sg[g] * wv * ialpha[g] * rdn;
+              if (ln < KG) { QP_CWG(U, cur, c1)[16 * g + ln][0] = -wv; QP_CWG(U, cur, c1)[16 * g + ln][1] = -gam; } /* stored negated: plain FMAs below */
+              /* a rank whose vector is zero in this column leaves its 1/alpha alone: d_prev / d_new is exactly 1 there, d * rcp(d) is not.
+               * (Columns above a rank's first nonzero are then exact no-ops: the result does not depend on where a sweep starts or on
+               * how the ranks are grouped into sweeps.) */
+              ialpha[g] = (wv == 0.0) ? ialpha[g] : ialpha[g] * dprev * rdn;
+              d0 = qp_readlane(dnew, kkg - 1); /* pivot of the column after this group's last rank */
+              nwv[g] = -wv; ngam[g] = -gam;
+            }
+            if (QP_PANEL_TIMING == 2) { double gg = ngam[0]; QP_OPAQUE_V(gg); const long long t = QP_CLOCK(); if (lane == 0) tdbg[9] += t - tc0; tc0 = t; }
+            if (ln == c1) dreg = d0; /* final pivot of the column = value after the last rank */
+            if (!QP_RECUR_DPP) QP_WAVE_SYNC();
+            /* rows of the block: lane = row.  Rows <= c1 are finished, their registers may be
+             * overwritten freely, so no selects: w_r -= w_j l ; l -= gamma w_r  (2 FMAs per rank) */
             double l = lcur;
-            /* the first eight entries come back from LDS together; with more than eight ranks an entry's registers are refilled with
-             * the entry eight ranks further right after its two FMAs, so that the second group's LDS latency runs under the first
-             * group's FMA chain (it used to be requested only after that chain: a second exposed round trip per column) */
-            const qp_pair QP_LDS_AS *tab = (const qp_pair QP_LDS_AS *)&QP_CWG(U, cur, c1)[0][0];
-            qp_pair cf[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) cf[r] = tab[r];
-            if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); const long long t = QP_CLOCK(); if (lane == 0) tdbg[10] += t - tc0; tc0 = t; }
-            if (K > 8 && kk > 8) {
-#pragma unroll
-              for (int r = 0; r < 8; r++) {
-                wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
-                l = QP_FMA(cf[r].y, wrow[r], l);
-                cf[r] = tab[(8 + r < K) ? 8 + r : r];
-                QP_SCHED_BARRIER();
-              }
-#pragma unroll
-              for (int r = 0; r < 8; r++) {
-                if (8 + r < K) {
-                  wrow[8 + r] = QP_FMA(cf[r].x, l, wrow[8 + r]);
-                  l = QP_FMA(cf[r].y, wrow[8 + r], l);
-                }
+            if (QP_RECUR_DPP) {
+              qp_apply_ranks_dpp<K, 0, 0, 8>(nwv[0], ngam[0], wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
+              if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16, false>(nwv[0], ngam[0], wrow, l);
+              if constexpr (G > 1) {
+                if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(nwv[1], ngam[1], wrow, l);
+                if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16, false>(nwv[1], ngam[1], wrow, l);
               }
             } else {
+              static_assert(QP_RECUR_DPP || G == 1, "the LDS form of the recurrence handles one rank group");
+              /* the first eight entries come back from LDS together; with more than eight ranks an entry's registers are refilled with
+               * the entry eight ranks further right after its two FMAs, so that the second group's LDS latency runs under the first
+               * group's FMA chain (it used to be requested only after that chain: a second exposed round trip per column) */
+              const qp_pair QP_LDS_AS *tab = (const qp_pair QP_LDS_AS *)&QP_CWG(U, cur, c1)[0][0];
+              qp_pair cf[8];
 #pragma unroll
-              for (int r = 0; r < 8; r++) {
-                wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
-                l = QP_FMA(cf[r].y, wrow[r], l);
+              for (int r = 0; r < 8; r++) cf[r] = tab[r];
+              if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); const long long t = QP_CLOCK(); if (lane == 0) tdbg[10] += t - tc0; tc0 = t; }
+              if (K > 8 && kk > 8) {
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                  wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
+                  l = QP_FMA(cf[r].y, wrow[r], l);
+                  cf[r] = tab[(8 + r < K) ? 8 + r : r];
+                  QP_SCHED_BARRIER();
+                }
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                  if (8 + r < K) {
+                    wrow[8 + r] = QP_FMA(cf[r].x, l, wrow[8 + r]);
+                    l = QP_FMA(cf[r].y, wrow[8 + r], l);
+                  }
+                }
+              } else {
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                  wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
+                  l = QP_FMA(cf[r].y, wrow[r], l);
+                }
               }
             }
-            if (ln > c1 && ln < jb) U.Ld[cur][ln][c1] = l;
+            const bool below = (ln > c1 && ln < jb); /* rows of the block below the column's diagonal entry */
+            if (below) U.Ld[cur][ln][c1] = l;
+            if constexpr (FS) { const double yc = qp_readlane(vsub, c1); vsub = QP_FMA(-(below ? l : 0.0), yc, vsub); }
             if (QP_PANEL_TIMING == 2) { double ll = l; QP_OPAQUE_V(ll); const long long t = QP_CLOCK(); if (lane == 0) tdbg[11] += t - tc0; }
+            QP_SCHED_BARRIER();
           }
-          QP_SCHED_BARRIER();
-        }
+        };
+        if constexpr (FOLD) { if (fuse) recurrence(std::true_type()); else recurrence(std::false_type()); }
+        else recurrence(std::false_type());
         if (QP_PANEL_TIMING == 1 && lane == 0) tdbg[9] += QP_CLOCK() - tp1;
         const long long tp2 = QP_CLOCK();
-        if (fuse) { /* the diagonal block is final: y_J = L_JJ^{-1} (b_J - contributions of the earlier blocks) */
-          double v = accp;
+        if constexpr (!FOLD) if (fuse) { /* the diagonal block is final: y_J = L_JJ^{-1} (b_J - contributions of the earlier blocks) */
           double lc = (lane > 0 && lane < jb) ? U.Ld[cur][lane][0] : 0.0;
 #pragma unroll 1
           for (int c = 0; c < jb; c++) {
             const int ln = QP_FRESH_LANE(lane);
             const double lcn = (ln > c + 1 && ln < jb) ? U.Ld[cur][ln][c + 1] : 0.0; /* in flight during this step (column NB is padding) */
-            const double yc = qp_readlane(v, c);
-            v = QP_FMA(-lc, yc, v);
+            const double yc = qp_readlane(vsub, c);
+            vsub = QP_FMA(-lc, yc, vsub);
             lc = lcn;
           }
-          if (lane < jb) { U.ys[cur][lane] = v; fs[J + lane] = v; }
         }
+        if (fuse && lane < jb) { U.ys[cur][lane] = vsub; fs[J + lane] = vsub; } /* the solved block of the right-hand side */
         /* diagonal block and pivots back to HBM (each lane re-reads what it wrote itself) */
         if (lane < jb) Dg[J + lane] = dreg;
         if (!QP_USQ) {
@@ -1833,6 +1846,8 @@ QPD void updown_big_panel(UpdownBigLds<K> QP_LDS_AS &U, const int lane, const in
     const double rdn = qp_rcp(dnew), rdp = qp_rcp(dprev);
     const double gam = -sg * wv * ialpha * rdn;
     if (ln < K) { U.cwg[c1][ln][0] = -wv; U.cwg[c1][ln][1] = -gam; }
+    /* (alpha is read by no formula here either; it stays because the coop sweeps hand it from block to block in their published tables
+     * (CO_UD_TAB, hst): taking it out changes that layout and three callers, which dense_updown's change does not need) */
     alpha = (wv == 0.0) ? alpha : alpha * dnew * rdp; /* zero in this column: exactly unchanged (see dense_updown) */
     ialpha = (wv == 0.0) ? ialpha : ialpha * dprev * rdn;
     { const double dfin = qp_readlane(dnew, kk - 1); if (ln == c1) dreg = dfin; }
