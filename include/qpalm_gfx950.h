@@ -14,6 +14,7 @@
  *   qpg_batch_warm_start                  qpalm_warm_start  include/qpalm.h:71-73, src/qpalm.c:322-399
  *   qpg_batch_solve / qpg_batch_iterate   qpalm_solve       include/qpalm.h:82,    src/qpalm.c:401-736
  *   qpg_batch_update_settings/bounds/q    qpalm_update_*    include/qpalm.h:95-126, src/qpalm.c:739-871
+ *   qpg_batch_*_device, qpg_batch_step_device   the same calls on arrays in device memory (no reference counterpart: it runs where its data is)
  *   qpg_batch_destroy                     qpalm_cleanup     include/qpalm.h:133,   src/qpalm.c:874-1096
  *   qpg_mat_vec / qpg_mat_tpose_vec       mat_vec / mat_tpose_vec          include/solver_interface.h:33,47
  *   qpg_ldlchol / qpg_ldlchol_matrix      ldlchol                           include/solver_interface.h:172
@@ -248,6 +249,32 @@ int  qpg_batch_update_q(qpg_batch *bt, const qpg_float *q);                     
  * unsolved and the counters of QPGStats restart.  QPG_ERR_INVALID before qpg_batch_setup or on a NULL array. */
 int  qpg_batch_update_Q_A(qpg_batch *bt, const qpg_float *Qx, const qpg_float *Ax);          /* host arrays [B][nnzQ_max], [B][nnzA_max] */
 int  qpg_batch_update_Q_A_device(qpg_batch *bt, const qpg_float *dQx, const qpg_float *dAx); /* the same layout, already in device memory (see qpg_batch_device_ptr) */
+/* ---- the per-step calls on arrays in DEVICE memory (of the context's device): the receding-horizon loop without the host.
+ * Each of the first five is its host form with the copy taken away: the same layout ([B][n] / [B][m] float64, contiguous; [B] qpg_int), the same
+ * state, validation (bmin <= bmax per member; a refused member keeps its bounds and reads QPG_ERROR until the next solve) and error codes
+ * (QPG_ERR_INVALID before qpg_batch_setup, on a NULL d_q, and with "Lower bound greater than upper bound").  Entries beyond a sized member's own
+ * n / m are ignored on input and zero on output.  Input arrays are only read; kernels of the batch's own instance move the data.
+ * Ordering: synchronous.  The caller guarantees that whatever produced the input arrays has finished; when a call returns the inputs have been
+ * read and the outputs are complete and visible to every stream.
+ * The latest accepted raw q / bounds, which qpg_batch_update_Q_A needs, are kept in a device-side record of B (n + 2 m) doubles (allocated by the
+ * first of these updates); host and device forms may be mixed in any order. */
+int  qpg_batch_update_bounds_device(qpg_batch *bt, const qpg_float *d_bmin, const qpg_float *d_bmax); /* either may be NULL */
+int  qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q);
+int  qpg_batch_warm_start_device(qpg_batch *bt, const qpg_float *d_x, const qpg_float *d_y);          /* either may be NULL */
+int  qpg_batch_get_solution_device(qpg_batch *bt, qpg_float *d_x, qpg_float *d_y);                    /* either may be NULL */
+int  qpg_batch_get_status_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_iter);              /* [B] each, either may be NULL */
+/* One whole step: update_bounds -> update_q -> warm start -> qpg_batch_solve -> get_solution -> get_status on the arrays below, all in device
+ * memory.  Returns QPG_ERR_INVALID at the end, after every member has been solved, if the bounds of any member were refused (that member
+ * solves on its old bounds). */
+typedef struct {
+  const qpg_float *bmin, *bmax, *q;      /* NULL = unchanged */
+  const qpg_float *warm_x, *warm_y;      /* used when warm == 2 (either may be NULL, not both) */
+  qpg_int          warm;                 /* 0 none, 1 = qpg_batch_warm_start_last, 2 = warm_x / warm_y */
+  qpg_float       *x, *y;                /* out, NULL = not wanted */
+  qpg_int         *status_val, *iter;    /* out [B], NULL = not wanted */
+  qpg_int         *rejected;             /* out [B], 1 = this member's bounds were refused (bmin > bmax), NULL = not wanted */
+} QPGDeviceStep;
+int  qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -53,6 +53,13 @@ class Stats(C.Structure):
                 ("n_seq_columns", c_int), ("n_sweep_columns", c_int), ("n_guard_refactor", c_int)]
 
 
+class DeviceStep(C.Structure):
+    """QPGDeviceStep: the arrays of one qpg_batch_step_device call, all addresses in device memory (0 = absent)."""
+    _fields_ = [("bmin", C.c_void_p), ("bmax", C.c_void_p), ("q", C.c_void_p), ("warm_x", C.c_void_p), ("warm_y", C.c_void_p),
+                ("warm", c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("status_val", C.c_void_p), ("iter", C.c_void_p),
+                ("rejected", C.c_void_p)]
+
+
 class QpgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("qpalm_gfx950 error %d: %s" % (code, msg))
@@ -102,6 +109,11 @@ def load(path=None):
     if hasattr(L, "qpg_batch_update_Q_A"):   # (absent from older builds of the library that tools/evidence/update_matrices_timing.py compares with)
         L.qpg_batch_update_Q_A.argtypes = [C.c_void_p, pf, pf]
         L.qpg_batch_update_Q_A_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "qpg_batch_step_device"):   # (absent from older builds of the library that tools/evidence/device_step_timing.py compares with)
+        for f in ("qpg_batch_update_bounds_device", "qpg_batch_warm_start_device", "qpg_batch_get_solution_device", "qpg_batch_get_status_device"):
+            getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qpg_batch_update_q_device.argtypes = [C.c_void_p, C.c_void_p]
+        L.qpg_batch_step_device.argtypes = [C.c_void_p, C.POINTER(DeviceStep)]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -152,6 +164,8 @@ SYMBOLS = [
     "qpg_kkt_update_entering_constraints", "qpg_kkt_update_leaving_constraints", "qpg_kkt_solve", "qpg_ldlchol_matrix", "qpg_sparse_matvec",
     "qpg_batch_begin_solve", "qpg_batch_get_info_all", "qpg_batch_get_stats_all", "qpg_ctx_hbm_copy_gbs", "qpg_ctx_hbm_read_gbs", "qpg_host_alloc", "qpg_host_free", "qpg_batch_set_problem_sized", "qpg_batch_set_problems",
     "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device", "qpg_batch_sparse_coop_info",
+    "qpg_batch_update_bounds_device", "qpg_batch_update_q_device", "qpg_batch_warm_start_device", "qpg_batch_get_solution_device",
+    "qpg_batch_get_status_device", "qpg_batch_step_device",
 ]
 
 

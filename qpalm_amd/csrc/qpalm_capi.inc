@@ -200,9 +200,20 @@ struct qpg_batch {
   int nnzA_in, nnzQ_in; /* nnzA_max / nnzQ_max as the caller gave them: the strides of the arrays qpg_batch_update_Q_A takes */
   std::vector<std::vector<int> > map_A, map_Q;
   void *val_maps_d = nullptr; bool val_maps_current = false;
-  /* the latest accepted raw q / bmin / bmax ([B][n], [B][m] x 2): created by the first qpg_batch_update_q / _bounds after a setup as a copy of the slab's
-   * arrays + the update (the device holds them scaled in place; the slab keeps the problem as set, which a second qpg_batch_setup returns to) */
-  std::vector<double> raw_q, raw_bmin, raw_bmax;
+  /* the latest accepted raw q / bmin / bmax ([B][n], [B][m], [B][m], one block in that order): created by the first qpg_batch_update_q / _bounds after
+   * a setup as a copy of the slab's arrays + the update (the device holds them scaled in place; the slab keeps the problem as set, which a second
+   * qpg_batch_setup returns to).  The host forms of the updates keep the record in raw_h; the device forms (qpg_batch_update_q_device /
+   * _bounds_device) keep it in raw_d, a block of the same layout in device memory that their kernels fill (allocated by the first of them).
+   * raw_cur says which is current -- 0: raw_h (empty: the slab), 1: raw_d, 2: both -- and whoever needs the other one copies it over at that
+   * moment, in one transfer (raw_need_host / raw_need_device). */
+  std::vector<double> raw_h;
+  void *raw_d = nullptr; int raw_cur = 0;
+  double *raw_q() { return raw_h.data(); }
+  double *raw_bmin() { return raw_h.data() + (size_t)B * n; }
+  double *raw_bmax() { return raw_h.data() + (size_t)B * n + (size_t)B * m; }
+  double *raw_d_q() const { return (double *)raw_d; }
+  double *raw_d_bmin() const { return (double *)raw_d + (size_t)B * n; }
+  double *raw_d_bmax() const { return (double *)raw_d + (size_t)B * n + (size_t)B * m; }
 };
 static void co_graphs_clear(qpg_batch *bt) {
   for (auto &g : bt->co_graphs) if (g.second.ready) RT_GRAPH_FREE(g.second.exec);
@@ -1073,7 +1084,7 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
   }
   bt->arena_clean = false;
   bt->is_setup = false;
-  bt->raw_q.clear(); bt->raw_bmin.clear(); bt->raw_bmax.clear(); /* the device gets the slab's q and bounds again */
+  bt->raw_h.clear(); bt->raw_cur = 0; /* the device gets the slab's q and bounds again (raw_d, if there is one, is stale until the next device-form update) */
   bt->val_maps_current = false;                                  /* (the members may have been set again) */
   V.B = bt->B; V.n = bt->n; V.m = bt->m; V.ld = bt->ld; V.nnzA = bt->nnzA; V.nnzQ = bt->nnzQ; V.nnzQf = bt->nnzQf;
   V.ls_hbm = bt->ctx->linesearch_hbm; V.seq_mode = bt->ctx->sequential_rank_sums;
@@ -1162,7 +1173,14 @@ extern "C" int qpg_batch_warm_start(qpg_batch *bt, const qpg_float *x, const qpg
   NEED_SETUP(bt, "qpg_batch_warm_start");
   if (x) RT_MEMCPY_H2D(bt->V.x, x, (size_t)bt->B * bt->n * sizeof(double));
   if (y) RT_MEMCPY_H2D(bt->V.y, y, (size_t)bt->B * bt->m * sizeof(double));
-  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, x ? 1 : 0, y ? 1 : 0);
+  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, x ? 1 : 0, y ? 1 : 0, (const double *)nullptr, (const double *)nullptr);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
+  return api_ok();
+}
+/* ... with x, y already in device memory: the kernel reads the caller's arrays */
+extern "C" int qpg_batch_warm_start_device(qpg_batch *bt, const qpg_float *d_x, const qpg_float *d_y) {
+  NEED_SETUP(bt, "qpg_batch_warm_start_device");
+  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, d_x ? 1 : 0, d_y ? 1 : 0, (const double *)d_x, (const double *)d_y);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
 }
@@ -1171,7 +1189,7 @@ extern "C" int qpg_batch_warm_start(qpg_batch *bt, const qpg_float *x, const qpg
  * horizon loop of an MPC controller without the round trip of x, y through the host. */
 extern "C" int qpg_batch_warm_start_last(qpg_batch *bt) {
   NEED_SETUP(bt, "qpg_batch_warm_start_last");
-  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, 2, 2);
+  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, 2, 2, (const double *)nullptr, (const double *)nullptr);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
 }
@@ -1557,6 +1575,35 @@ extern "C" int qpg_batch_get_solution(qpg_batch *bt, qpg_float *x, qpg_float *y)
   if (y) RT_MEMCPY_D2H(y, bt->V.sol_y, (size_t)bt->B * bt->m * sizeof(double));
   return api_ok();
 }
+/* ... into arrays in device memory: a kernel writes them */
+extern "C" int qpg_batch_get_solution_device(qpg_batch *bt, qpg_float *d_x, qpg_float *d_y) {
+  NEED_SETUP(bt, "qpg_batch_get_solution_device");
+  if (!d_x && !d_y) return api_ok();
+  BT_LAUNCH(bt, k_get_solution, blocks_for(bt), 0, bt->V, (double *)d_x, (double *)d_y);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_get_solution failed: " + std::string(RT_LAST_ERROR()));
+  return api_ok();
+}
+/* info->status_val / info->iter of every QP into [B] arrays in device memory.  The QPG_ERROR marks of refused updates live on the host
+ * (host_status): while there are any, they go to the device as one flag per member (the line-search scratch is idle between solves).
+ * flags_in (device, [B] ints) / flags_out: see k_get_status */
+static int status_to_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_iter, const int *flags_in, qpg_int *flags_out) {
+  if (!d_status_val && !d_iter && !flags_out) return api_ok();
+  const int *err_d = nullptr;
+  if (d_status_val && std::find(bt->host_status.begin(), bt->host_status.end(), (int)QPG_ERROR) != bt->host_status.end()) {
+    std::vector<int> err((size_t)bt->B);
+    for (int b = 0; b < bt->B; b++) err[b] = bt->host_status[b] == QPG_ERROR ? 1 : 0;
+    int *scratch = (int *)bt->V.ls_idx + bt->B; /* (behind the flags of k_update_bounds: [B][ls_stride] ints, ls_stride >= 2) */
+    RT_MEMCPY_H2D(scratch, err.data(), err.size() * sizeof(int));
+    err_d = scratch;
+  }
+  BT_LAUNCH(bt, k_get_status, (bt->B + bt->threads - 1) / bt->threads, 0, bt->V, err_d, (int64_t *)d_status_val, (int64_t *)d_iter, flags_in, (int64_t *)flags_out);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_get_status failed: " + std::string(RT_LAST_ERROR()));
+  return api_ok();
+}
+extern "C" int qpg_batch_get_status_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_iter) {
+  NEED_SETUP(bt, "qpg_batch_get_status_device");
+  return status_to_device(bt, d_status_val, d_iter, nullptr, nullptr);
+}
 
 static int vec_lookup(qpg_batch *bt, const char *name, qpg_int idx, size_t elem, char **ptr, size_t *count) {
   void *p; size_t bytes;
@@ -1672,13 +1719,47 @@ extern "C" int qpg_batch_update_settings(qpg_batch *bt, const QPGSettings *s) { 
   return api_ok();
 }
 
-/* creates the record of the raw q / bounds from the slab (see qpg_batch) */
-static void raw_record(qpg_batch *bt) {
-  if (!bt->raw_q.empty()) return;
+/* The record of the raw q / bounds (see qpg_batch).  raw_need_host: raw_h is current afterwards -- created from the slab, or fetched from the
+ * device mirror where a device-form update was the last to write; raw_need_device: the same for raw_d.  The caller then sets raw_cur to the side
+ * it writes. */
+static void raw_need_host(qpg_batch *bt) {
   const size_t B = bt->B, n = bt->n, m = bt->m;
-  bt->raw_q.assign(bt->harr<double>(H_Q, 0), bt->harr<double>(H_Q, 0) + B * n);
-  bt->raw_bmin.assign(bt->harr<double>(H_BMIN, 0), bt->harr<double>(H_BMIN, 0) + B * m);
-  bt->raw_bmax.assign(bt->harr<double>(H_BMAX, 0), bt->harr<double>(H_BMAX, 0) + B * m);
+  if (bt->raw_cur == 1) {
+    bt->raw_h.resize(B * (n + 2 * m));
+    RT_MEMCPY_D2H(bt->raw_h.data(), bt->raw_d, bt->raw_h.size() * sizeof(double));
+    bt->raw_cur = 2;
+  }
+  if (!bt->raw_h.empty()) return;
+  bt->raw_h.resize(B * (n + 2 * m));
+  memcpy(bt->raw_q(), bt->harr<double>(H_Q, 0), B * n * sizeof(double));
+  memcpy(bt->raw_bmin(), bt->harr<double>(H_BMIN, 0), B * m * sizeof(double));
+  memcpy(bt->raw_bmax(), bt->harr<double>(H_BMAX, 0), B * m * sizeof(double));
+}
+static int raw_need_device(qpg_batch *bt) {
+  const size_t B = bt->B, n = bt->n, m = bt->m;
+  if (!bt->raw_d && RT_MALLOC(&bt->raw_d, B * (n + 2 * m) * sizeof(double)) != 0) { bt->raw_d = nullptr; return 1; }
+  if (bt->raw_cur >= 1) return 0;
+  if (!bt->raw_h.empty()) RT_MEMCPY_H2D(bt->raw_d, bt->raw_h.data(), bt->raw_h.size() * sizeof(double));
+  else { /* nothing updated since the setup: the slab's arrays */
+    RT_MEMCPY_H2D(bt->raw_d_q(), bt->harr<double>(H_Q, 0), B * n * sizeof(double));
+    if (m > 0) {
+      RT_MEMCPY_H2D(bt->raw_d_bmin(), bt->harr<double>(H_BMIN, 0), B * m * sizeof(double));
+      RT_MEMCPY_H2D(bt->raw_d_bmax(), bt->harr<double>(H_BMAX, 0), B * m * sizeof(double));
+    }
+  }
+  return 0;
+}
+
+/* after k_update_bounds: the flags come back (one int per member), refused members are marked QPG_ERROR until the next solve */
+static int bounds_flags(qpg_batch *bt, const int *bad_d, std::vector<int> &bad) {
+  bad.assign((size_t)bt->B, 0);
+  RT_MEMCPY_D2H(bad.data(), bad_d, bad.size() * sizeof(int));
+  int nbad = 0;
+  for (size_t b = 0; b < bad.size(); b++) {
+    if (bad[b]) { bt->host_status[b] = QPG_ERROR; nbad++; }
+    else if (bt->host_status[b] == QPG_ERROR) bt->host_status[b] = QPG_UNSOLVED; /* valid bounds now: qpalm_solve overwrites the status (qpalm.c:401-420) */
+  }
+  return nbad;
 }
 
 extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, const qpg_float *bmax) { /* qpalm.c:793-827 */
@@ -1691,32 +1772,62 @@ extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, con
     if (bmax) RT_MEMCPY2D_H2D(bt->V.ls_key + m, ls * sizeof(double), bmax, m * sizeof(double), m * sizeof(double), B);
   }
   int *bad_d = (int *)bt->V.ls_idx; /* scratch: one flag per QP */
-  BT_LAUNCH(bt, k_update_bounds, blocks_for(bt), 0, bt->V, bmin ? 1 : 0, bmax ? 1 : 0, bad_d);
+  BT_LAUNCH(bt, k_update_bounds, blocks_for(bt), 0, bt->V, bmin ? 1 : 0, bmax ? 1 : 0, bad_d, (const double *)bt->V.ls_key, (const double *)(bt->V.ls_key + m),
+            (long long)ls, (double *)nullptr, (double *)nullptr);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_bounds failed: " + std::string(RT_LAST_ERROR()));
-  std::vector<int> bad(B, 0);
-  RT_MEMCPY_D2H(bad.data(), bad_d, B * sizeof(int));
-  int nbad = 0;
-  raw_record(bt);
-  for (size_t b = 0; b < B; b++) {
+  std::vector<int> bad;
+  const int nbad = bounds_flags(bt, bad_d, bad);
+  raw_need_host(bt);
+  bt->raw_cur = 0;
+  for (size_t b = 0; b < B; b++)
     if (!bad[b] && m > 0) { /* accepted: the member's raw bounds from now on (qpg_batch_update_Q_A) */
-      if (bmin) memcpy(bt->raw_bmin.data() + b * m, bmin + b * m, m * sizeof(double));
-      if (bmax) memcpy(bt->raw_bmax.data() + b * m, bmax + b * m, m * sizeof(double));
+      if (bmin) memcpy(bt->raw_bmin() + b * m, bmin + b * m, m * sizeof(double));
+      if (bmax) memcpy(bt->raw_bmax() + b * m, bmax + b * m, m * sizeof(double));
     }
-    if (bad[b]) { bt->host_status[b] = QPG_ERROR; nbad++; }
-    else if (bt->host_status[b] == QPG_ERROR) bt->host_status[b] = QPG_UNSOLVED; /* valid bounds now: qpalm_solve overwrites the status (qpalm.c:401-420) */
+  if (nbad) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
+  return api_ok();
+}
+/* ... with the bounds already in device memory: the kernel reads the caller's arrays and keeps the record of the accepted raw values in
+ * the device mirror; only the flags (one int per member) come back.  rejected (device, [B], or NULL): the flags for the caller */
+static int update_bounds_device(qpg_batch *bt, const qpg_float *d_bmin, const qpg_float *d_bmax, qpg_int *rejected) {
+  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)");
+  int *bad_d = (int *)bt->V.ls_idx;
+  BT_LAUNCH(bt, k_update_bounds, blocks_for(bt), 0, bt->V, d_bmin ? 1 : 0, d_bmax ? 1 : 0, bad_d, (const double *)d_bmin, (const double *)d_bmax,
+            (long long)bt->m, bt->raw_d_bmin(), bt->raw_d_bmax());
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_bounds failed: " + std::string(RT_LAST_ERROR()));
+  bt->raw_cur = 1;
+  std::vector<int> bad;
+  const int nbad = bounds_flags(bt, bad_d, bad);
+  if (rejected) {
+    const int rc = status_to_device(bt, nullptr, nullptr, bad_d, rejected);
+    if (rc != QPG_OK) return rc;
   }
   if (nbad) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
   return api_ok();
+}
+extern "C" int qpg_batch_update_bounds_device(qpg_batch *bt, const qpg_float *d_bmin, const qpg_float *d_bmax) {
+  NEED_SETUP(bt, "qpg_batch_update_bounds_device");
+  return update_bounds_device(bt, d_bmin, d_bmax, nullptr);
 }
 
 extern "C" int qpg_batch_update_q(qpg_batch *bt, const qpg_float *q) { /* qpalm.c:829-871 */
   NEED_SETUP(bt, "qpg_batch_update_q");
   if (!q) return fail(QPG_ERR_INVALID, "qpg_batch_update_q: NULL");
   RT_MEMCPY_H2D(bt->V.q, q, (size_t)bt->B * bt->n * sizeof(double));
-  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V);
+  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V, (const double *)nullptr, (double *)nullptr);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_q failed: " + std::string(RT_LAST_ERROR()));
-  raw_record(bt);
-  memcpy(bt->raw_q.data(), q, (size_t)bt->B * bt->n * sizeof(double));
+  raw_need_host(bt);
+  bt->raw_cur = 0;
+  memcpy(bt->raw_q(), q, (size_t)bt->B * bt->n * sizeof(double));
+  return api_ok();
+}
+extern "C" int qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q) {
+  NEED_SETUP(bt, "qpg_batch_update_q_device");
+  if (!d_q) return fail(QPG_ERR_INVALID, "qpg_batch_update_q_device: NULL");
+  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)");
+  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V, (const double *)d_q, bt->raw_d_q());
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_q failed: " + std::string(RT_LAST_ERROR()));
+  bt->raw_cur = 1;
   return api_ok();
 }
 
@@ -1748,11 +1859,12 @@ static int update_Q_A_device(qpg_batch *bt, const double *dQx, size_t strideQ, c
     }
   }
   /* the raw q and bounds a fresh setup would upload */
-  const bool rec = !bt->raw_q.empty();
-  RT_MEMCPY_H2D(V.q, rec ? bt->raw_q.data() : bt->harr<double>(H_Q, 0), B * n * sizeof(double));
+  if (bt->raw_cur == 1) raw_need_host(bt); /* the device forms of the updates wrote last: their record comes over (one transfer) */
+  const bool rec = !bt->raw_h.empty();
+  RT_MEMCPY_H2D(V.q, rec ? bt->raw_q() : bt->harr<double>(H_Q, 0), B * n * sizeof(double));
   if (m > 0) {
-    RT_MEMCPY_H2D(V.bmin, rec ? bt->raw_bmin.data() : bt->harr<double>(H_BMIN, 0), B * m * sizeof(double));
-    RT_MEMCPY_H2D(V.bmax, rec ? bt->raw_bmax.data() : bt->harr<double>(H_BMAX, 0), B * m * sizeof(double));
+    RT_MEMCPY_H2D(V.bmin, rec ? bt->raw_bmin() : bt->harr<double>(H_BMIN, 0), B * m * sizeof(double));
+    RT_MEMCPY_H2D(V.bmax, rec ? bt->raw_bmax() : bt->harr<double>(H_BMAX, 0), B * m * sizeof(double));
   }
   BT_LAUNCH(bt, k_update_Q_A, blocks_for(bt), 0, V, dQx, (long long)strideQ, dAx, (long long)strideA, (const int32_t *)mapQ_d, (const int32_t *)mapA_d,
             (const int32_t *)same_d, setup_scalars(bt), (int)bt->settings.scaling);
@@ -1780,6 +1892,32 @@ extern "C" int qpg_batch_update_Q_A(qpg_batch *bt, const qpg_float *Qx, const qp
   return update_Q_A_device(bt, bt->V.Qfx, (size_t)bt->nnzQf, bt->V.Atx, (size_t)bt->nnzA);
 }
 
+/* One receding-horizon step on arrays in device memory: update_bounds -> update_q -> warm start -> solve -> get_solution -> get_status, each the
+ * device form above (or qpg_batch_warm_start_last / qpg_batch_solve).  A refused member (bmin > bmax) keeps its bounds and solves on them; the call
+ * then returns QPG_ERR_INVALID after the whole step has run.  Any other error ends the step where it occurs. */
+extern "C" int qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io) {
+  NEED_SETUP(bt, "qpg_batch_step_device");
+  if (!io) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: NULL");
+  if (io->warm < 0 || io->warm > 2) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: warm must be 0, 1 or 2");
+  if (io->warm == 2 && !io->warm_x && !io->warm_y) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: warm = 2 needs warm_x or warm_y");
+  int rc, refused = 0;
+  if (io->bmin || io->bmax) {
+    rc = update_bounds_device(bt, io->bmin, io->bmax, io->rejected);
+    if (rc == QPG_ERR_INVALID) refused = 1;
+    else if (rc != QPG_OK) return rc;
+  } else if (io->rejected) {
+    if ((rc = status_to_device(bt, nullptr, nullptr, nullptr, io->rejected)) != QPG_OK) return rc;
+  }
+  if (io->q && (rc = qpg_batch_update_q_device(bt, io->q)) != QPG_OK) return rc;
+  if (io->warm == 1 && (rc = qpg_batch_warm_start_last(bt)) != QPG_OK) return rc;
+  if (io->warm == 2 && (rc = qpg_batch_warm_start_device(bt, io->warm_x, io->warm_y)) != QPG_OK) return rc;
+  if ((rc = qpg_batch_solve(bt)) != QPG_OK) return rc;
+  if ((rc = qpg_batch_get_solution_device(bt, io->x, io->y)) != QPG_OK) return rc;
+  if ((rc = qpg_batch_get_status_device(bt, io->status_val, io->iter)) != QPG_OK) return rc;
+  if (refused) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
+  return api_ok();
+}
+
 extern "C" void qpg_batch_destroy(qpg_batch *bt) {
   if (!bt) return;
   if (bt->arena_thread.joinable()) bt->arena_thread.join();
@@ -1788,6 +1926,7 @@ extern "C" void qpg_batch_destroy(qpg_batch *bt) {
   if (bt->sparse_d) RT_FREE(bt->sparse_d);
   if (bt->co_tab_d) RT_FREE(bt->co_tab_d);
   if (bt->val_maps_d) RT_FREE(bt->val_maps_d);
+  if (bt->raw_d) RT_FREE(bt->raw_d);
   co_graphs_clear(bt);
   host_slab_free(bt->hslab, bt->hslab_bytes);
   delete bt;

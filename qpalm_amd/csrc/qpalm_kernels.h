@@ -290,12 +290,16 @@ __global__ __launch_bounds__(QP_T) void k_lobpcg(qpg_view V) {
   }
 }
 
-__global__ __launch_bounds__(QP_T) void k_warm_start(qpg_view V, int has_x, int has_y) {
+/* src_x / src_y: the caller's own arrays in device memory ([B][n] / [B][m], qpg_batch_warm_start_device), read here instead of a copy the host
+ * placed in x / y; NULL = the host placed them (has_x / has_y = 1) or they are not needed */
+__global__ __launch_bounds__(QP_T) void k_warm_start(qpg_view V, int has_x, int has_y, const double *src_x, const double *src_y) {
   __shared__ IterShared I;
   for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     __syncthreads();
     if (threadIdx.x == 0) I.s = V.sc[b];
+    if (src_x && has_x == 1) for (int j = threadIdx.x; j < a.n; j += QP_T) a.x()[j] = src_x[(size_t)b * V.n + j];
+    if (src_y && has_y == 1) for (int i = threadIdx.x; i < a.m; i += QP_T) a.y()[i] = src_y[(size_t)b * V.m + i];
     __syncthreads();
     dev_warm_start(V, a, b, has_x, has_y, I);
     if (threadIdx.x == 0) {
@@ -392,14 +396,16 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_solve(qpg_view V, int bud
   }
 }
 
-/* qpalm_update_bounds, device part (qpalm.c:819-826): the host wrote the raw bounds */
-/* The raw bounds are staged in the line-search scratch (ls_key: [b][0..m) = bmin, [b][m..2m) = bmax; idle between solves).
- * Validation (bmin <= bmax, qpalm.c:806-817) happens here too: bad[b] = 1 leaves the QP's bounds untouched. */
-__global__ __launch_bounds__(QP_T) void k_update_bounds(qpg_view V, int has_bmin, int has_bmax, int *bad) {
+/* qpalm_update_bounds, device part (qpalm.c:819-826).  The raw bounds of member b are src_min + b * stride and src_max + b * stride: the host form
+ * stages them in the line-search scratch (ls_key: [b][0..m) = bmin, [b][m..2m) = bmax, stride ls_stride; idle between solves), the device form
+ * (qpg_batch_update_bounds_device) passes the caller's own [B][m] arrays.  Validation (bmin <= bmax, qpalm.c:806-817) happens here too: bad[b] = 1
+ * leaves the QP's bounds untouched.  raw_min / raw_max ([B][m], or NULL): the mirror of the accepted raw bounds (qpg_batch::raw_d) is filled here. */
+__global__ __launch_bounds__(QP_T) void k_update_bounds(qpg_view V, int has_bmin, int has_bmax, int *bad, const double *src_min, const double *src_max,
+                                                        long long stride, double *raw_min, double *raw_max) {
   __shared__ int s_bad;
   for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
-    const double *smin = V.ls_key + (size_t)b * V.ls_stride, *smax = smin + V.m; /* batch stride m: rows of the host arrays */
+    const double *smin = src_min + (size_t)b * stride, *smax = src_max + (size_t)b * stride;
     int mine = 0;
     if (has_bmin && has_bmax)
       for (int i = threadIdx.x; i < a.m; i += QP_T) mine |= (smin[i] > smax[i]) ? 1 : 0;
@@ -415,18 +421,27 @@ __global__ __launch_bounds__(QP_T) void k_update_bounds(qpg_view V, int has_bmin
     for (int i = threadIdx.x; i < a.m; i += QP_T) {
       if (has_bmin) a.bmin()[i] = sc ? a.E()[i] * smin[i] : smin[i];
       if (has_bmax) a.bmax()[i] = sc ? a.E()[i] * smax[i] : smax[i];
+      if (has_bmin && raw_min) raw_min[(size_t)b * V.m + i] = smin[i];
+      if (has_bmax && raw_max) raw_max[(size_t)b * V.m + i] = smax[i];
     }
   }
 }
 
-/* qpalm_update_q, device part (qpalm.c:829-871): the host wrote the raw q */
-__global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V) {
+/* qpalm_update_q, device part (qpalm.c:829-871).  src = NULL: the host wrote the raw q into place; else the caller's own [B][n] array in device
+ * memory (qpg_batch_update_q_device), copied into place here first, and into raw_q (the mirror of the raw values, qpg_batch::raw_d) */
+__global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V, const double *src, double *raw_q) {
   __shared__ IterShared I;
   const qpg_settings &st = *V.settings;
   for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     __syncthreads();
     if (threadIdx.x == 0) I.s = V.sc[b];
+    if (src)
+      for (int j = threadIdx.x; j < a.n; j += QP_T) {
+        const double qj = src[(size_t)b * V.n + j];
+        a.q()[j] = qj;
+        if (raw_q) raw_q[(size_t)b * V.n + j] = qj;
+      }
     __syncthreads();
     if (I.s.has_scaling) {
       const double c_old = I.s.sc_c, cinv_old = I.s.sc_cinv, mg = -1 / I.s.gamma;
@@ -461,6 +476,27 @@ __global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V) {
       }
     }
     __syncthreads();
+  }
+}
+
+/* qpg_batch_get_solution_device: the stored solutions into the caller's [B][n] / [B][m] arrays (either may be NULL); entries beyond a member's own
+ * n / m are written as zeros */
+__global__ __launch_bounds__(QP_T) void k_get_solution(qpg_view V, double *out_x, double *out_y) {
+  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+    const QpArrays a = qp_arrays(V, b);
+    if (out_x) for (int j = threadIdx.x; j < V.n; j += QP_T) out_x[(size_t)b * V.n + j] = (j < a.n) ? a.sol_x()[j] : 0.0;
+    if (out_y) for (int i = threadIdx.x; i < V.m; i += QP_T) out_y[(size_t)b * V.m + i] = (i < a.m) ? a.sol_y()[i] : 0.0;
+  }
+}
+
+/* qpg_batch_get_status_device: info->status_val and info->iter of every QP into the caller's [B] arrays of 64-bit integers, one thread per QP.
+ * err ([B], or NULL): members the host marked QPG_ERROR (a refused update) read as such.  flags_out ([B], or NULL) = flags_in[b] != 0
+ * (0 everywhere without flags_in): the "rejected" array of qpg_batch_step_device.  Any output may be NULL. */
+__global__ __launch_bounds__(QP_T) void k_get_status(qpg_view V, const int *err, int64_t *status_val, int64_t *iter, const int *flags_in, int64_t *flags_out) {
+  for (int b = blockIdx.x * QP_T + threadIdx.x; b < V.B; b += gridDim.x * QP_T) {
+    if (status_val) status_val[b] = (err && err[b]) ? QPG_ERROR : V.sc[b].status;
+    if (iter) iter[b] = V.sc[b].iter;
+    if (flags_out) flags_out[b] = (flags_in && flags_in[b]) ? 1 : 0;
   }
 }
 

@@ -24,6 +24,7 @@ class Context:
         if rc != 0:
             raise QpgError(rc, self.L.qpg_last_error().decode())
         self.h = h
+        self.device = int(device)
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -221,6 +222,110 @@ class QpalmBatch:
     def update_Q_A_device(self, ptr_Qx, ptr_Ax):
         """the same from device memory: raw addresses of [B][nnzQ_max] / [B][nnzA_max] float64 arrays (e.g. torch tensors' data_ptr())"""
         self._check(self.L.qpg_batch_update_Q_A_device(self.h, C.c_void_p(int(ptr_Qx)), C.c_void_p(int(ptr_Ax))))
+
+    # -- the per-step calls on arrays in device memory ---------------------------------------------------
+    def _dev(self, v, shape, what, dtype="float64"):
+        """(address or None, is_tensor) of an array in the context's device memory: None, a raw address (int, as update_Q_A_device takes) or a torch
+        tensor, which must sit on the context's device, be contiguous and have this dtype and shape -- ValueError otherwise, before anything is
+        launched.  Under emulation device memory is host memory: CPU tensors there."""
+        if v is None:
+            return None, False
+        if isinstance(v, (int, np.integer)):
+            return int(v), False
+        if not hasattr(v, "data_ptr"):
+            raise ValueError("%s: expected a torch tensor or a raw address, got %s" % (what, type(v).__name__))
+        import torch
+        want = getattr(torch, dtype)
+        on_gpu = self.ctx.backend != "host-emulation"
+        if v.device.type != ("cuda" if on_gpu else "cpu") or (on_gpu and v.device.index != self.ctx.device):
+            raise ValueError("%s: tensor on %s, the batch lives on %s" % (what, v.device, "cuda:%d" % self.ctx.device if on_gpu else "cpu (emulation)"))
+        if v.dtype != want:
+            raise ValueError("%s: dtype %s, expected %s" % (what, v.dtype, want))
+        if tuple(v.shape) != tuple(shape):
+            raise ValueError("%s: shape %r, expected %r" % (what, tuple(v.shape), tuple(shape)))
+        if not v.is_contiguous():
+            raise ValueError("%s: tensor is not contiguous" % what)
+        return int(v.data_ptr()), True
+
+    def _dev_args(self, *specs):
+        """addresses (c_void_p or None) of several arrays, all checked first; then, if any was a tensor, torch's current stream on the device is
+        synchronised -- the calls are synchronous: whatever produced the inputs must have finished"""
+        got = [self._dev(v, shape, what, dtype) for v, shape, what, dtype in specs]
+        if any(t for _, t in got) and self.ctx.backend != "host-emulation":
+            import torch
+            torch.cuda.current_stream(self.ctx.device).synchronize()
+        return [C.c_void_p(a) if a is not None else None for a, _ in got]
+
+    def _empty(self, shape, dtype="float64"):
+        import torch
+        dev = "cpu" if self.ctx.backend == "host-emulation" else "cuda:%d" % self.ctx.device
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+
+    def update_bounds_device(self, bmin=None, bmax=None):
+        """update_bounds from [B][m] float64 arrays in device memory (torch tensors or raw addresses); returns the code like update_bounds"""
+        a, b = self._dev_args((bmin, (self.B, self.m), "bmin", "float64"), (bmax, (self.B, self.m), "bmax", "float64"))
+        return self.L.qpg_batch_update_bounds_device(self.h, a, b)
+
+    def update_q_device(self, q):
+        if q is None:
+            raise ValueError("q: expected a torch tensor or a raw address")
+        a, = self._dev_args((q, (self.B, self.n), "q", "float64"))
+        self._check(self.L.qpg_batch_update_q_device(self.h, a))
+
+    def warm_start_device(self, x=None, y=None):
+        a, b = self._dev_args((x, (self.B, self.n), "x", "float64"), (y, (self.B, self.m), "y", "float64"))
+        self._check(self.L.qpg_batch_warm_start_device(self.h, a, b))
+
+    def solution_device(self, out=None):
+        """(x [B][n], y [B][m]) written in device memory; out = (x, y): tensors or raw addresses to fill (either may be None), else new tensors"""
+        x, y = out if out is not None else (self._empty((self.B, self.n)), self._empty((self.B, self.m)))
+        a, b = self._dev_args((x, (self.B, self.n), "x", "float64"), (y, (self.B, self.m), "y", "float64"))
+        self._check(self.L.qpg_batch_get_solution_device(self.h, a, b))
+        return x, y
+
+    def status_device(self, out=None):
+        """(status_val [B], iter [B]) as int64, written in device memory; out as for solution_device"""
+        sv, it = out if out is not None else (self._empty((self.B,), "int64"), self._empty((self.B,), "int64"))
+        a, b = self._dev_args((sv, (self.B,), "status_val", "int64"), (it, (self.B,), "iter", "int64"))
+        self._check(self.L.qpg_batch_get_status_device(self.h, a, b))
+        return sv, it
+
+    STEP_OUT = ("x", "y", "status_val", "iter", "rejected")
+
+    def step_device(self, bmin=None, bmax=None, q=None, warm="last", out=None):
+        """One receding-horizon step without the host (qpg_batch_step_device): new bounds / q (None = unchanged), warm start ("last" = every QP's own
+        last solution, None = none, (x, y) = given arrays, one of which may be None), solve, and the results written in device memory.  All arrays are
+        torch tensors on the context's device or raw addresses.  out: a dict with any of the keys x, y, status_val, iter, rejected (absent or None =
+        not wanted); without it all five are allocated.  Returns (rc, out): rc = 0, or -2 (QPG_ERR_INVALID) when some member's bounds were refused --
+        the step has run all the same, that member on its old bounds, and out["rejected"] says which."""
+        if out is None:
+            out = dict(x=self._empty((self.B, self.n)), y=self._empty((self.B, self.m)), status_val=self._empty((self.B,), "int64"),
+                       iter=self._empty((self.B,), "int64"), rejected=self._empty((self.B,), "int64"))
+        unknown = set(out) - set(self.STEP_OUT)
+        if unknown:
+            raise ValueError("out: unknown keys %r" % sorted(unknown))
+        if warm is None:
+            mode, wx, wy = 0, None, None
+        elif isinstance(warm, str):
+            if warm != "last":
+                raise ValueError("warm: 'last', None or (x, y)")
+            mode, wx, wy = 1, None, None
+        else:
+            mode = 2
+            wx, wy = warm
+            if wx is None and wy is None:
+                raise ValueError("warm: (x, y) with both None")
+        nB, n, m = self.B, self.n, self.m
+        a = self._dev_args((bmin, (nB, m), "bmin", "float64"), (bmax, (nB, m), "bmax", "float64"), (q, (nB, n), "q", "float64"),
+                           (wx, (nB, n), "warm x", "float64"), (wy, (nB, m), "warm y", "float64"),
+                           (out.get("x"), (nB, n), "out x", "float64"), (out.get("y"), (nB, m), "out y", "float64"),
+                           (out.get("status_val"), (nB,), "out status_val", "int64"), (out.get("iter"), (nB,), "out iter", "int64"),
+                           (out.get("rejected"), (nB,), "out rejected", "int64"))
+        io = capi.DeviceStep(a[0], a[1], a[2], a[3], a[4], mode, a[5], a[6], a[7], a[8], a[9])
+        rc = self.L.qpg_batch_step_device(self.h, C.byref(io))
+        if rc not in (0, -2):
+            self._check(rc)
+        return rc, out
 
     # -- results --------------------------------------------------------------------------------
     def info(self, b=0):
