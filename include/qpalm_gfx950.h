@@ -229,6 +229,13 @@ int  qpg_batch_sparse_info(qpg_batch *bt, qpg_int idx, qpg_int *nnzL, qpg_int *d
  * at least four times shallower -- the factorisation and the solves run at the latency of the tree's height.  Changes rounding, not
  * what is computed. */
 int  qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, qpg_int *levels);
+/* Member idx's sparse factor as it stands, in the factor's own numbering (qpg_batch_sparse_perm maps it to the caller's): Lp = column pointers
+ * (nf + 1 entries; nf = n, or n + m in KKT mode under "sparse_kkt"), Li / Lx = row indices (ascending within a column) and values of the strict
+ * lower part (nnzL of qpg_batch_sparse_info entries each; the pattern is that of ALL rows of A, so entries may be zero), D = the nf pivots.  Any
+ * output may be NULL.  For tests and diagnostics (the sparse counterpart of qpg_batch_get_factor, which stays refused on a sparse batch): the
+ * index arrays are copied back from the device.  QPG_ERR_UNSUPPORTED on a batch with dense factors and when B > max_slots (a slot then holds
+ * whichever QP ran last). */
+int  qpg_batch_get_sparse_factor(qpg_batch *bt, qpg_int idx, qpg_int *Lp, qpg_int *Li, qpg_float *Lx, qpg_float *D);
 /* The launch plan of member idx under the context option "sparse_coop" = 1, made by qpg_batch_setup from the level sets of the member's
  * elimination tree (patterns only: qpg_batch_update_Q_A leaves it valid): launches per factorisation, launches per Newton solve (permutation in,
  * forward levels, D, backward levels, permutation out) and the largest grid among them.  Consecutive levels that one workgroup finishes in one

@@ -102,6 +102,8 @@ def load(path=None):
         L.qpg_batch_sparse_perm.argtypes = [C.c_void_p, c_int, pi, pi]
     if hasattr(L, "qpg_batch_sparse_coop_info"):   # (absent from older builds of the library that tools/evidence/sparse_coop_timing.py compares with)
         L.qpg_batch_sparse_coop_info.argtypes = [C.c_void_p, c_int, pi, pi, pi]
+    if hasattr(L, "qpg_batch_get_sparse_factor"):   # (absent from older builds of the library that the tools/evidence scripts compare with)
+        L.qpg_batch_get_sparse_factor.argtypes = [C.c_void_p, c_int, pi, pi, pf, pf]
     L.qpg_batch_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.qpg_batch_update_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
     L.qpg_batch_update_bounds.argtypes = [C.c_void_p, pf, pf]
@@ -165,7 +167,7 @@ SYMBOLS = [
     "qpg_batch_begin_solve", "qpg_batch_get_info_all", "qpg_batch_get_stats_all", "qpg_ctx_hbm_copy_gbs", "qpg_ctx_hbm_read_gbs", "qpg_host_alloc", "qpg_host_free", "qpg_batch_set_problem_sized", "qpg_batch_set_problems",
     "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device", "qpg_batch_sparse_coop_info",
     "qpg_batch_update_bounds_device", "qpg_batch_update_q_device", "qpg_batch_warm_start_device", "qpg_batch_get_solution_device",
-    "qpg_batch_get_status_device", "qpg_batch_step_device",
+    "qpg_batch_get_status_device", "qpg_batch_step_device", "qpg_batch_get_sparse_factor",
 ]
 
 

@@ -1036,6 +1036,33 @@ extern "C" int qpg_batch_sparse_perm(qpg_batch *bt, qpg_int idx, qpg_int *perm, 
   return api_ok();
 }
 
+/* member idx's sparse factor as it stands in device memory, in the factor's own numbering (qpg_batch_sparse_perm maps it): column pointers (nf + 1
+ * entries, nf = n, or n + m in KKT mode), row indices and values of the strict lower part (nnz(L) of qpg_batch_sparse_info each), pivots (nf).  Any
+ * output may be NULL.  The symbolic arrays are copied back from the device (the analysis is not kept on the host); a slot holds QP idx's values only
+ * while B <= max_slots (as qpg_batch_get_factor). */
+extern "C" int qpg_batch_get_sparse_factor(qpg_batch *bt, qpg_int idx, qpg_int *Lp, qpg_int *Li, qpg_float *Lx, qpg_float *D) {
+  if (!bt || !bt->is_setup) return fail(QPG_ERR_INVALID, "qpg_batch_get_sparse_factor: batch is not set up");
+  if (!bt->sparse) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_get_sparse_factor: the batch keeps dense factors (qpg_batch_get_factor reads those)");
+  if (idx < 0 || idx >= bt->B) return fail(QPG_ERR_INVALID, "qpg_batch_get_sparse_factor: bad index");
+  if (bt->B > bt->nslots) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_get_sparse_factor: a slot belongs to a QP only while B <= max_slots");
+  const qpg_view &V = bt->V;
+  const HostProblem &P = bt->probs[(size_t)idx];
+  const size_t nf = (size_t)(bt->kkt ? P.n + P.m : P.n), nz = (size_t)bt->sp_nnz[(size_t)idx], b = (size_t)idx;
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, RT_LAST_ERROR());
+  std::vector<int> tmp(std::max(nf + 1, nz));
+  if (Lp) {
+    RT_MEMCPY_D2H(tmp.data(), V.sp_Lp + b * ((size_t)V.nfac + 1), (nf + 1) * sizeof(int));
+    for (size_t j = 0; j <= nf; j++) Lp[j] = tmp[j];
+  }
+  if (Li && nz) {
+    RT_MEMCPY_D2H(tmp.data(), V.sp_Li + b * (size_t)V.sp_nnzL, nz * sizeof(int));
+    for (size_t e = 0; e < nz; e++) Li[e] = tmp[e];
+  }
+  if (Lx && nz) RT_MEMCPY_D2H(Lx, V.sp_Lx + b * (size_t)V.sp_nnzL, nz * sizeof(double));
+  if (D) RT_MEMCPY_D2H(D, V.Dg + b * (size_t)V.nfac, nf * sizeof(double));
+  return api_ok();
+}
+
 /* the per-QP scalars qpalm_setup leaves (seq_hint is the member's own) */
 static qpg_scalars setup_scalars(const qpg_batch *bt) {
   qpg_scalars sc0;

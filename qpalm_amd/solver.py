@@ -168,6 +168,18 @@ class QpalmBatch:
         self._check(self.L.qpg_batch_sparse_perm(self.h, int(b), perm.ctypes.data_as(C.POINTER(capi.c_int)), C.byref(lev)))
         return perm, int(lev.value)
 
+    def sparse_factor(self, b=0):
+        """(Lp, Li, Lx, D) of member b's sparse factor as it stands on the device, in the factor's own numbering (sparse_perm maps it): column
+        pointers (nf + 1; nf = n, or n + m in KKT mode), row indices and values of the strict lower part, pivots.  Raises on a batch with dense
+        factors (factor() reads those) and when the batch has more members than factor slots"""
+        n, m = self.dims[b]
+        nf = n + m if int(self.settings.factorization_method) == 0 else n
+        nnz = self.sparse_info(b)[0]
+        Lp, Li = np.zeros(nf + 1, dtype=np.int64), np.zeros(nnz, dtype=np.int64)
+        Lx, D = np.zeros(nnz), np.zeros(nf)
+        self._check(self.L.qpg_batch_get_sparse_factor(self.h, int(b), iptr(Lp), iptr(Li), fptr(Lx), fptr(D)))
+        return Lp, Li, Lx, D
+
     def sparse_coop_info(self, b=0):
         """(factor_launches, solve_launches, max_grid): member b's launch plan under the context option "sparse_coop" = 1; (0, 0, 0) when the batch runs
         on one workgroup per QP; raises on a batch with dense factors"""
