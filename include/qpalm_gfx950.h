@@ -118,7 +118,7 @@ typedef struct {
   qpg_int placement;             /* where the QP's last solve ran: (XCC, SE, SH, CU) key << 16 | arrival index of the workgroup on
                                     that CU << 8 | panel wavefront << 4 | SIMD of wavefront 0 (qp_place_panel_wave) */
   qpg_int lobpcg_iter, nonconvex; /* LOBPCG iterations; settings->nonconvex of THIS QP after set_settings_nonconvex (:171-183) */
-  qpg_int n_fused_solve;         /* of n_solve: solves whose forward substitution was done by the last update sweep (L read once, not twice) */
+  qpg_int n_fused_solve;         /* of n_solve: solves whose forward substitution was done by the last update sweep or by the factorisation before it (L read once, not twice) */
   qpg_int n_seq_columns;         /* columns of the update sweeps whose pivots the per-column guard re-summed as the reference's running pivot (a pivot shrank by 2^8 or more) */
   qpg_int n_sweep_columns;       /* ... out of this many columns of diagonal-block recurrences */
   qpg_int n_guard_refactor;      /* Newton steps redone with a fresh factorisation because the direction from an updated factor was not finite */
@@ -146,6 +146,11 @@ void qpg_ctx_destroy(qpg_ctx *ctx);
  *   "ld_align"              leading dimension of the factor panels in doubles (16 = every column on a 128-byte line)
  *   "sweep_ranks"           16 (default) or 32 ranks per update sweep (32: the multi-pass sweep, bit-identical factors, slower)
  *   "kkt_compact"           1 = FACTORIZE_KKT factorises the variables + ACTIVE constraints only and spreads the factor out on demand
+ *   "factor_fused_solve"    1 (default) = on the Schur path a factorisation that a Newton solve follows (ldlcholQAtsigmaA / ldlchol, then
+ *                           ldlsolveLD_neg_dphi) carries the forward substitution of that solve: -dphi sits in LDS behind the factorisation's own
+ *                           blocks, every finished block column is applied to it at once, and the solve streams L once instead of twice.  d is bit
+ *                           for bit what the separate pass gives (same fma chain per entry); counted in n_fused_solve.  Where the vector does not
+ *                           fit the LDS, in KKT mode, in coop mode and with the sparse factor the solve stays whole.  0 = never (A/B runs, tests).
  *   "place_panel_wave"      0 / 1 / 2: SIMD placement of the sweeps' panel wavefronts (0 = the hardware's own)
  *   "sequential_rank_sums"  how an update sweep sums a column's pivots.  -1 (default) = a prefix tree, and any column in which a pivot
  *                           shrinks by 2^8 or more inside the sweep is summed again as the reference's running pivot (per-column guard); the running

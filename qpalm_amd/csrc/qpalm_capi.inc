@@ -121,6 +121,9 @@ struct qpg_ctx {
   int sweep_ranks;         /* most ranks per sweep of the rank update: 16 (default) or 32 (the multi-pass form of dense_updown: half the panel traffic per
                               rank, bit-identical factors -- but measured SLOWER on MI355X in round 4, DESIGN section 7: 4.4-4.8 k against 5.2-5.3 k QP/s;
                               the sweep is bound by its serial chain, not by the bytes) */
+  int factor_fused_solve;  /* 1 (default): on the Schur path a factorisation that a Newton solve follows carries the solve's forward substitution (dense_factor:
+                              the right-hand side sits in LDS behind the factorisation's own blocks where it fits) -- L is streamed once less, d is bit for bit
+                              the same; 0: the separate forward pass (A/B runs, tests) */
   int kkt_compact;         /* 1 (default): KKT mode's form + factorise skips the inactive constraints' unit rows (qpalm_kkt.h: kkt_form_compact / kkt_expand) */
   int sequential_rank_sums; /* the pivots of an update sweep as d_r = d_{r-1} + p_r, rank after rank (the reference's order; 15 dependent steps per column) instead of as a
                               prefix tree (4 steps): -1 (default) for QPs whose factor can get near-singular -- nonconvex ones and those whose Q has a column
@@ -225,7 +228,7 @@ extern "C" int qpg_ctx_create(int device, qpg_ctx **out) {
   std::string why;
   if (RT_DEVICE_INIT(device, why) != 0) return fail(QPG_ERR_NO_DEVICE, "qpg_ctx_create: " + why);
   qpg_ctx *c = new qpg_ctx();
-  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->sparse_factor = -1; c->sparse_kkt = 0; c->sparse_coop = 0; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
+  c->device = device; c->lds_bytes = QPG_LDS_DEFAULT; c->max_slots = 512; c->update_rank_threshold = -1; c->small_workgroups = 1; c->place_panel_wave = 0; c->narrow_rows = 1; c->coop = -1; c->coop_workgroups = 256; c->coop_max_batch = 4; c->coop_rank_threshold = -2; c->coop_updates = 2; c->coop_test_kill = 0; c->queue_order = 1; c->coop_graphs = 1; c->ld_align = 16; c->sweep_ranks = 16; c->kkt_compact = 1; c->factor_fused_solve = 1; c->sparse_factor = -1; c->sparse_kkt = 0; c->sparse_coop = 0; c->sparse_ordering = -1; c->sparse_lds = 1; c->sparse_gpw = 0; c->linesearch_hbm = 0; c->sequential_rank_sums = -1;
   for (int k = 0; k < 5; k++) { c->mv_buf[k] = nullptr; c->mv_cap[k] = 0; }
   *out = c;
   return api_ok();
@@ -263,6 +266,7 @@ extern "C" int qpg_ctx_set_option(qpg_ctx *ctx, const char *name, qpg_int value)
   else if (!strcmp(name, "queue_order")) ctx->queue_order = value ? 1 : 0;
   else if (!strcmp(name, "sweep_ranks")) { if (value != 16 && value != 32) return fail(QPG_ERR_INVALID, "sweep_ranks must be 16 or 32"); ctx->sweep_ranks = (int)value; }
   else if (!strcmp(name, "kkt_compact")) ctx->kkt_compact = value ? 1 : 0;
+  else if (!strcmp(name, "factor_fused_solve")) ctx->factor_fused_solve = value ? 1 : 0;
   else if (!strcmp(name, "sparse_factor")) ctx->sparse_factor = (value < 0) ? -1 : (value ? 1 : 0);
   else if (!strcmp(name, "sparse_kkt")) ctx->sparse_kkt = value ? 1 : 0;
   else if (!strcmp(name, "sparse_coop")) { if (value != 0 && value != 1) return fail(QPG_ERR_INVALID, "sparse_coop must be 0 or 1"); ctx->sparse_coop = (int)value; }
@@ -1126,6 +1130,7 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
   V.wst_stride = (int)QPG_WST_STRIDE(bt->nfac);
   V.sweep_ranks = bt->ctx->sweep_ranks;
   V.kkt_compact = bt->ctx->kkt_compact;
+  V.factor_fused_solve = bt->ctx->factor_fused_solve;
   V.kkt = bt->kkt; V.nfac = bt->nfac;
   if (ensure_dual_slots(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (LD_Q slots)");
   V.sparse = 0; V.sp_co_G = 0; V.sp_co_wv = nullptr;

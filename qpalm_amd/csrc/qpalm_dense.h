@@ -383,12 +383,12 @@ struct FactorLds {
 struct FactorStage { double As[2][QP_FKC][QP_FAS]; };
 
 template <int NTJ, int NCT>
-QP_NI_FGEMM void factor_panel_update(double *L_, const double *Dg_, char *stage_, int n_, int ld_, int J_, int tbase_, int k0_, int k1_) {
+QPD void factor_panel_update_body(double *L_, const double *Dg_, char *stage_, int n_, int ld_, int J_, int tbase_, int k0_, int k1_) {
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_), J = QP_UNIFORM(J_), tbase = QP_UNIFORM(tbase_), k0 = QP_UNIFORM(k0_), k1 = QP_UNIFORM(k1_);
   qp_gdouble *L = (qp_gdouble *)L_;
   const qp_gdouble *Dg = (const qp_gdouble *)Dg_;
   FactorStage QP_LDS_AS &F = *QP_LDS_ARG(FactorStage, stage_);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = QP_FRESH_TID(), lane = tid & 63, wid = tid >> 6; /* (fresh: nothing derived from it outlives this pass) */
   const int l15 = lane & 15, l4 = lane >> 4;
   constexpr bool PAIR = (NTJ == 2);
   constexpr int NBW = 16 * NCT; /* block width */
@@ -508,21 +508,34 @@ QP_NI_FGEMM void factor_panel_update(double *L_, const double *Dg_, char *stage_
   }
 }
 
-/* Step (3) of dense_factor as its own function: one row per thread, the row's 32 panel entries live
+/* The right-hand side of a Newton solve that rides on the factorisation (dense_factor, fs): an n-vector behind FactorLds and FactorStage */
+#define QP_FACTOR_YS_OFF (((sizeof(FactorLds) + 15) & ~(size_t)15) + sizeof(FactorStage))
+QPD bool factor_solve_fits(const int n, const int lds_bytes) { return QP_FACTOR_YS_OFF + (size_t)n * sizeof(double) <= (size_t)lds_bytes; }
+
+/* the panel update as a real call (the multi-workgroup factorisation, co_factor_trailing) */
+template <int NTJ, int NCT>
+QP_NI_FGEMM void factor_panel_update(double *L_, const double *Dg_, char *stage_, int n_, int ld_, int J_, int tbase_, int k0_, int k1_) {
+  factor_panel_update_body<NTJ, NCT>(L_, Dg_, stage_, n_, ld_, J_, tbase_, k0_, k1_);
+}
+
+/* Step (3) of dense_factor: one row per thread, the row's 32 panel entries live
  * in registers (64 VGPRs), L and 1/D of the diagonal block come as LDS broadcasts. */
 #ifndef QP_NI_FROWS
-#define QP_NI_FROWS QPNI
+#define QP_NI_FROWS QPD /* inline: dense_factor keeps ONE register frame per factorisation (profiles/factor_scratch) */
 #endif
-QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const int ld_, const int J_, const int jb_) {
+/* fuse_ != 0: the forward substitution of the solve that follows rides along (dense_factor, fs): y_i <- fma(-l_ic, y_c, y_i), c ascending,
+ * with the l_ic just stored and the block's y_c that factor_diag_block left in LDS -- row i on thread (i - J - jb) % QP_T, as in dense_solve */
+QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const int ld_, const int J_, const int jb_, const int fuse_ = 0) {
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_), J = QP_UNIFORM(J_), jb = QP_UNIFORM(jb_); /* wave-uniform arguments back to SGPRs */
   qp_gdouble *L = (qp_gdouble *)L_;
   FactorLds QP_LDS_AS &F = *QP_LDS_ARG(FactorLds, lds_);
+  double QP_LDS_AS *ys = QP_LDS_ARG(double, lds_ + QP_FACTOR_YS_OFF);
   constexpr int NB = QP_FNB;
   /* FULL = all 32 columns exist (every block but possibly the last): no per-column conditionals */
-  auto rows = [&](auto full) QP_ALWAYS_INLINE {
-    constexpr bool FULL = decltype(full)::value;
+  auto rows = [&](auto full, auto fused) QP_ALWAYS_INLINE {
+    constexpr bool FULL = decltype(full)::value, FUSE = decltype(fused)::value;
 #pragma unroll 1
-    for (int i = J + jb + threadIdx.x; i < n; i += QP_T) {
+    for (int i = J + jb + QP_FRESH_TID(); i < n; i += QP_T) {
       qp_gdouble *base = L + (size_t)J * ld + i;
       double u[NB];
 #pragma unroll
@@ -542,12 +555,25 @@ QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const i
       }
       int ld2 = ld;
       QP_OPAQUE(ld2); /* store addresses are recomputed: 32 live column pointers would cost 64 VGPRs */
+      if (FUSE) {
+        double acc = ys[i];
 #pragma unroll
-      for (int c = 0; c < NB; c++)
-        if (FULL || c < jb) base[(size_t)c * ld2] = u[c] * F.dv[c];
+        for (int c = 0; c < NB; c++)
+          if (FULL || c < jb) {
+            const double l = u[c] * F.dv[c];
+            base[(size_t)c * ld2] = l;
+            acc = QP_FMA(-l, ys[J + c], acc);
+          }
+        ys[i] = acc;
+      } else {
+#pragma unroll
+        for (int c = 0; c < NB; c++)
+          if (FULL || c < jb) base[(size_t)c * ld2] = u[c] * F.dv[c];
+      }
     }
   };
-  if (jb == NB) rows(std::true_type()); else rows(std::false_type());
+  if (QP_UNIFORM(fuse_) != 0) { if (jb == NB) rows(std::true_type(), std::true_type()); else rows(std::false_type(), std::true_type()); }
+  else { if (jb == NB) rows(std::true_type(), std::false_type()); else rows(std::false_type(), std::false_type()); }
 }
 
 /* Step (2) of dense_factor as its own function (own register allocation): the staged 32 x 32 diagonal block (rows
@@ -559,10 +585,10 @@ QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const i
 #ifndef QP_NI_FDIAG
 #define QP_NI_FDIAG QPNI
 #endif
-QP_NI_FDIAG void factor_diag_block(char *lds_) {
+QPD void factor_diag_block_body(char *lds_, const int fuse = 0, const int J = 0, const int jb = 0) {
   FactorLds QP_LDS_AS &F = *QP_LDS_ARG(FactorLds, lds_);
   constexpr int NB = QP_FNB;
-  const int r = (int)(threadIdx.x & (NB - 1));
+  const int tx = QP_FRESH_TID(), r = tx & (NB - 1);
   double p[NB];
 #pragma unroll
   for (int c = 0; c < NB; c++) p[c] = F.Ld[r][c];
@@ -576,29 +602,55 @@ QP_NI_FDIAG void factor_diag_block(char *lds_) {
       p[c2] = QP_FMA(-lic, s, p[c2]);       /* meaningful for rows r >= c2; rows above the diagonal are never read */
     }
     p[c] = lic;
-    if (r == c && threadIdx.x < NB) { F.dv[c] = 1.0 / dc; F.dg[c] = dc; } /* reciprocal pivot for the panel rows */
+    if (r == c && tx < NB) { F.dv[c] = 1.0 / dc; F.dg[c] = dc; } /* reciprocal pivot for the panel rows */
   }
-  if (threadIdx.x < NB) {
+  if (tx < NB) {
 #pragma unroll
     for (int c = 0; c < NB; c++) if (r > c) F.Ld[r][c] = p[c];
   }
+  if (fuse) { /* the block's 32 unknowns of the solve that rides along: dense_solve's block step with the row of L still in registers */
+    double QP_LDS_AS *ys = QP_LDS_ARG(double, lds_ + QP_FACTOR_YS_OFF);
+    const int lane = tx; /* wavefront 0 */
+    double v = (lane < jb) ? ys[J + lane] : 0.0;
+#pragma unroll
+    for (int c = 0; c < NB; c++) {
+      const double yc = qp_readlane(v, c);
+      const double l = (r > c && r < jb) ? p[c] : 0.0;
+      v = QP_FMA(-l, yc, v);
+    }
+    if (lane < jb) ys[J + lane] = v;
+  }
 }
 
-template <int RPT>
+QP_NI_FDIAG void factor_diag_block(char *lds_) { factor_diag_block_body(lds_); } /* as a real call (co_factor_diag) */
+
 #ifndef QP_NI_FACTOR
 #define QP_NI_FACTOR QPNI
 #endif
-QP_NI_FACTOR void dense_factor(double *L_, double *Dg_, int n_, int ld_, char *lds_, int64_t *tdbg_) {
-  const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_); /* wave-uniform arguments back to SGPRs */
+/* The three steps are inline (factor_panel_update_body, factor_diag_block_body, factor_panel_rows): one register frame per factorisation instead
+ * of one per step and call (~140 calls, ~5300 dwords per lane through scratch at n = 1000; profiles/factor_scratch). */
+QP_NI_FACTOR void dense_factor(double *La_, double *Dga_, int n_, int ld_, char *ldsa_, int64_t *tdbga_, const double *fb_ = nullptr, double *fs_ = nullptr) {
+  const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_); /* wave-uniform arguments back to SGPRs ... */
+  /* ... the pointers too: as VGPR pairs they stayed live -- spilled and reloaded -- through every loop of every step */
+  double *L_ = QP_UNIFORM_PTR(La_), *Dg_ = QP_UNIFORM_PTR(Dga_);
+  char *lds_ = QP_UNIFORM_PTR(ldsa_);
+  int64_t *tdbg_ = QP_UNIFORM_PTR(tdbga_);
+  /* fs (or null): where the solve that follows this factorisation expects y = L^{-1} b (dense_solve's mode 2 takes it from there); b = -fb.  The caller has checked factor_solve_fits: the vector lives in LDS at QP_FACTOR_YS_OFF while the columns are finished
+   * in ascending order -- the order of the forward substitution -- so L is not streamed a second time for it. */
+  qp_gdouble *fs = (qp_gdouble *)QP_UNIFORM_PTR(fs_);
+  const qp_gdouble *fb = (const qp_gdouble *)QP_UNIFORM_PTR(fb_);
+  const int fuse = (fs != nullptr) ? 1 : 0; /* (from the scalar copy: a uniform branch) */
+  double QP_LDS_AS *ys = QP_LDS_ARG(double, lds_ + QP_FACTOR_YS_OFF);
   int64_t QP_LDS_AS *tdbg = (int64_t QP_LDS_AS *)tdbg_; /* the timers live in the kernel's static LDS */
   qp_gdouble *L = (qp_gdouble *)L_, *Dg = (qp_gdouble *)Dg_;
   FactorLds QP_LDS_AS &F = *QP_LDS_ARG(FactorLds, lds_);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int NB = QP_FNB;
   __syncthreads();
+  if (fuse) for (int i = QP_FRESH_TID(); i < n; i += QP_T) ys[i] = fb[i] * -1; /* ldlsolveLD_neg_dphi's right-hand side (first read behind the barriers of block column 0) */
   long long tq0 = QP_CLOCK();
   for (int J = 0; J < n; J += NB) {
     const int jb = (n - J < NB) ? (n - J) : NB;
+    int tid = QP_FRESH_TID(); /* read again ahead of every step: see QP_FRESH_TID */
     /* ---- (1) panel update on the matrix cores.  Left-looking over 64-column super-blocks: at the start of a
      * super-block its 64 columns receive the contributions of ALL earlier columns (the panel is streamed once per
      * 64 columns); its second 32-column block then only needs the 32 columns just finished. ---------------- */
@@ -612,11 +664,11 @@ QP_NI_FACTOR void dense_factor(double *L_, double *Dg_, int n_, int ld_, char *l
           const int rem = ntiles - tbase;
           const int ntj = (rem + QP_NW - 1) / QP_NW; /* same for every wavefront */
           if (super) {
-            if (ntj <= 1) factor_panel_update<1, 4>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
-            else factor_panel_update<2, 4>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
+            if (ntj <= 1) factor_panel_update_body<1, 4>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
+            else factor_panel_update_body<2, 4>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
           } else {
-            if (ntj <= 1) factor_panel_update<1, 2>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
-            else factor_panel_update<2, 2>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
+            if (ntj <= 1) factor_panel_update_body<1, 2>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
+            else factor_panel_update_body<2, 2>(L_, Dg_, stage, n, ld, J, tbase, k0, k1);
           }
         }
         if (tid == 0) { /* entries of L re-read: the panel rows once per pass group, the block rows once per pass */
@@ -629,13 +681,15 @@ QP_NI_FACTOR void dense_factor(double *L_, double *Dg_, int n_, int ld_, char *l
     if (tid == 0) { const long long tq1 = QP_CLOCK(); tdbg[4] += tq1 - tq0; tq0 = tq1; }
     /* ---- (2) diagonal block: staged in LDS by all threads (rows beyond the matrix = identity), factorised by
      * wavefront 0 in registers (factor_diag_block), written back by all threads ---------------------------------- */
+    tid = QP_FRESH_TID();
     for (int e = tid; e < NB * NB; e += QP_T) {
       const int c = e / NB, r = e % NB;
       F.Ld[r][c] = (r >= c && r < jb) ? L[(size_t)(J + c) * ld + (J + r)] : ((r == c) ? 1.0 : 0.0);
     }
     __syncthreads();
-    if (wid == 0) factor_diag_block(lds_);
+    if ((tid >> 6) == 0) factor_diag_block_body(lds_, fuse, J, jb);
     __syncthreads();
+    tid = QP_FRESH_TID();
     for (int e = tid; e < jb * jb; e += QP_T) {
       const int c = e / jb, r = e % jb;
       if (r > c) L[(size_t)(J + c) * ld + (J + r)] = F.Ld[r][c];
@@ -643,10 +697,11 @@ QP_NI_FACTOR void dense_factor(double *L_, double *Dg_, int n_, int ld_, char *l
     if (tid < jb) Dg[J + tid] = F.dg[tid];
     if (tid == 0) { const long long tq1 = QP_CLOCK(); tdbg[5] += tq1 - tq0; tq0 = tq1; }
     /* ---- (3) rows below the block: l_ic = (p_ic - sum_{c1<c} u_ic1 l_c,c1) / d_c ---------------- */
-    factor_panel_rows(L_, lds_, n, ld, J, jb);
+    factor_panel_rows(L_, lds_, n, ld, J, jb, fuse);
     __syncthreads();
-    if (tid == 0) { const long long tq1 = QP_CLOCK(); tdbg[6] += tq1 - tq0; tq0 = tq1; }
+    if (QP_FRESH_TID() == 0) { const long long tq1 = QP_CLOCK(); tdbg[6] += tq1 - tq0; tq0 = tq1; }
   }
+  if (fuse) for (int i = QP_FRESH_TID(); i < n; i += QP_T) fs[i] = ys[i];
   __syncthreads();
 }
 

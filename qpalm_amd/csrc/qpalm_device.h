@@ -100,6 +100,7 @@ typedef emu_double4 qp_double4;
 #define QP_OPAQUE_V(x) do { } while (0)
 #define QP_FRESH_LANE(lane) (lane)
 #define QP_CALL_BLOCK() 1
+#define QP_FRESH_TID() ((int)threadIdx.x)
 #define QP_ALWAYS_INLINE
 /* emulation: one "CU", wavefront w sits on "SIMD" w & 3 (exercises the panel-wave rotation) */
 #define QP_HW_CU_KEY() 0
@@ -141,6 +142,15 @@ static __device__ __forceinline__ int qp_fresh_lane_() {
   return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
 }
 #define QP_FRESH_LANE(lane) qp_fresh_lane_()
+/* the thread id as a value the optimiser cannot connect with earlier reads of it: what a step of a long function derives from it (row and
+ * tile indices, LDS addresses) is then computed inside that step instead of once ahead of the function's outermost loop, where it would stay
+ * live -- in spilled registers -- across every other step (dense_factor: the steps of a block column) */
+static __device__ __forceinline__ int qp_fresh_tid_() {
+  int t = (int)threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t & 1023;
+}
+#define QP_FRESH_TID() qp_fresh_tid_()
 /* A wave-uniform "true" the compiler cannot see through: `if (QP_CALL_BLOCK()) callee(...)` gives the call a basic block
  * of its own behind a scalar branch.  Why: ROCm 7.2's register allocator saves caller-saved VGPRs around a call with
  * copies at the top of the block that holds the call; when that block starts with the `s_or_b64 exec` closing a divergent

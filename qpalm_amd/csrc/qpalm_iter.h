@@ -248,7 +248,7 @@ QPN void dev_warm_start(const qpg_view &V, const QpArrays &a, int b, int has_x, 
  * factorisation plumbing
  * =========================================================================================== */
 template <int RPT>
-QPN void dev_factor(const qpg_view &V, int n, double *L, double *Dg, char *lds, int64_t *tdbg) { dense_factor<RPT>(L, Dg, n, V.ld, lds, tdbg); }
+QPN void dev_factor(const qpg_view &V, int n, double *L, double *Dg, char *lds, int64_t *tdbg, const double *fb = nullptr, double *fs = nullptr) { dense_factor(L, Dg, n, V.ld, lds, tdbg, fb, fs); } /* fb, fs: see dense_factor */
 /* RPT = rows of the factor per thread in the update sweep (registers); RPT == 0 is the large-factor form (more than
  * 4 QP_T rows: the running vectors live in HBM, dense_updown_big) */
 template <int RPT>
@@ -1025,6 +1025,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
     }
     const long long t0 = QP_CLOCK();
     double gersh_ub = 0.0;
+    int factor_fused = 0; /* (wave-uniform, kept scalar) the Newton solve's forward substitution rides on this pass's factorisation (dense_factor, fs) */
     if constexpr (SPARSE) {
       /* sparse factor (qpalm_sparse.h): rows entering / leaving the active set are rank-1 updates along their elimination-tree
        * paths where that pays, a refactorisation otherwise; changed penalties likewise (la == 4: ldlupdate_sigma_changed as path updates with the scaled
@@ -1074,7 +1075,9 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
       double *Lt = (la == 7) ? LQ : L, *Dt = (la == 7) ? DgQ : Dg;
       gersh_ub = form_schur(V, b, n, Lt, la == 5, la == 1 || la == 5, (la == 1 || la == 3) && (prox != 0), gam, I.S, lds);
       if (tid == 0) I.s.ticks_dbg[3] += QP_CLOCK() - t0;
-      if (la != 5) dev_factor<RPT>(V, n, Lt, Dt, lds, I.s.ticks_dbg);
+      /* a Newton step solves right after the factorisation: its forward substitution rides on it where the right-hand side fits the LDS */
+      factor_fused = QP_UNIFORM((int)(!SPARSE && (la == 1 || la == 3) && kind == QP_KIND_NEWTON && !V.kkt && !V.offload && V.factor_fused_solve && factor_solve_fits(n, V.lds_bytes)));
+      if (la != 5) dev_factor<RPT>(V, n, Lt, Dt, lds, I.s.ticks_dbg, factor_fused ? a.dphi() : nullptr, factor_fused ? a.d() : nullptr); /* (d <- L^{-1} (-dphi)) */
       if (dual_init) { /* qpalm.c:459-468: LD_Q is ready, the dual objective of the starting point (scalar branch) */
         const double dobj = dev_dual_objective(V, a, b, LQ, DgQ, I, lds);
         if (tid == 0) { I.s.dual_objective = dobj; I.s.dual_pending = 0; }
@@ -1117,7 +1120,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
         }
       } else
       if (!V.kkt && !resume) {
-        const bool fused = (RPT > 0) && !QP_NOFUSE && (action == 2) && !V.offload;
+        const bool fused = ((RPT > 0) && !QP_NOFUSE && (action == 2) && !V.offload) || factor_fused;
         if (!fused) for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1;
         __syncthreads();
         dense_solve(L, Dg, n, V.ld, a.d(), lds, V.lds_bytes, I.s.ticks_dbg, fused ? 2 : 0); /* 2: d already holds L^{-1} (-dphi) */
@@ -1131,7 +1134,7 @@ QPN void dev_solve(const qpg_view &V, int b, int slot, int budget, int fresh, It
         if (action == 3) { I.s.n_factor_Q++; I.s.ticks_factor += t1 - t0; }
         if (action == 2) { if (!V.kkt) I.s.n_rank1 += nchange; I.s.n_sweeps = (int)I.s.ticks_dbg[QPG_CNT_SWEEPS]; I.s.ticks_update += t1 - t0; }
         I.s.n_solve++; I.s.ticks_solve += t2 - t1;
-        if (!V.kkt && (RPT > 0) && !QP_NOFUSE && action == 2 && (SPARSE || !V.offload)) I.s.n_fused_solve++;
+        if ((!V.kkt && (RPT > 0) && !QP_NOFUSE && action == 2 && (SPARSE || !V.offload)) || factor_fused) I.s.n_fused_solve++;
         I.s.last_fact = action;
       }
       QP_OPAQUE(a.b);

@@ -222,11 +222,11 @@ QPNI void kkt_newton(const qpg_view *Vp, int b_, double *L, double *Dg, double *
   int kna = QP_UNIFORM(I.s.kkt_na);
   if (action == 1 && can_compact) {
     kna = kkt_form_compact(V, a, b, L, gamma, prox, I, list);
-    dense_factor<RPT>(L, Dg, n + kna, ld, lds, I.s.ticks_dbg);
+    dense_factor(L, Dg, n + kna, ld, lds, I.s.ticks_dbg);
   } else {
     if (kna >= 0 && (action == 2 || action == 5)) { kkt_expand(V, a, L, Dg, kna, list, lds); kna = -1; } /* 5: only make the layout full (a read of the factor) */
     if (action == 1 || action == 3) { kkt_form(V, a, b, L, gamma, prox); kna = -1; }
-    if (action == 1 || action == 4) { dense_factor<RPT>(L, Dg, np, ld, lds, I.s.ticks_dbg); kna = -1; }
+    if (action == 1 || action == 4) { dense_factor(L, Dg, np, ld, lds, I.s.ticks_dbg); kna = -1; }
   }
   __syncthreads();
   if (tid == 0) I.s.kkt_na = kna;

@@ -82,7 +82,7 @@ typedef struct {
                                            the next pass refactorises and solves again instead of stepping (dev_solve; the oracle restates the same guard); the count of such passes */
   int32_t dual_pending, kkt_first; /* kkt_first: solver->first_factorization (types.h:176), KKT path; dual_pending: the factor of Q and the initial dual objective (qpalm.c:459-468) are still to be computed */
   /* work counters (device side statistics for the roofline accounting in bench.py) */
-  int32_t n_refactor, n_factor_Q, n_sweeps, n_rank1, n_solve, n_sigma_updates, n_boost_gamma, n_fused_solve; /* n_fused_solve: Newton solves whose forward substitution rode on the last update sweep (L streamed once less) */
+  int32_t n_refactor, n_factor_Q, n_sweeps, n_rank1, n_solve, n_sigma_updates, n_boost_gamma, n_fused_solve; /* n_fused_solve: Newton solves whose forward substitution rode on the last update sweep or on the factorisation (L streamed once less) */
   int64_t ticks_total, ticks_factor, ticks_update, ticks_solve, ticks_linesearch, ticks_resid;
   int64_t ticks_dbg[QPG_NDBG]; /* [0..15] fine-grained phase timers (100 MHz ticks), see QPGStats.ms_dbg;
                                   [16..] work counters written by the linear-algebra functions themselves (QPG_CNT_*) */
@@ -92,7 +92,8 @@ typedef struct {
 typedef struct {
   int32_t B, n, m, ld, nnzA, nnzQ, nnzQf, nslots, lds_bytes, update_rank_threshold, ls_stride, wst_stride, place_panel_wave, narrow_rows;
   int32_t offload, sweep_ranks; /* sweep_ranks: most ranks one sweep of the rank update applies (16, the default, or 32 = the multi-pass form of dense_updown: bit-identical factors, measured slower).  coop mode: 1 = dev_solve suspends at its linear-algebra site for factorisations and Newton solves (sparse coop mode: always 1, path updates stay on the workgroup), 2 = for rank updates too */
-  int32_t kkt_compact, kkt_pad; /* 1: KKT mode factorises the variables + ACTIVE constraints only and spreads the factor out (qpalm_kkt.h) */
+  int32_t kkt_compact, factor_fused_solve; /* kkt_compact 1: KKT mode factorises the variables + ACTIVE constraints only and spreads the factor out (qpalm_kkt.h);
+                                               factor_fused_solve 1: a factorisation that a Newton solve follows carries that solve's forward substitution (dense_factor) */
   int32_t kkt, nfac; /* kkt != 0: FACTORIZE_KKT, the factor slots hold the (n+m) x (n+m) KKT panel; nfac = rows of a factor slot
                         (n, or n + m in KKT mode); ld = its leading dimension */
   /* problem data.  A: CSC m x n.  At: CSC of A' (n x m) with the permutation into A's entries.
