@@ -287,6 +287,34 @@ typedef struct {
   qpg_int         *rejected;             /* out [B], 1 = this member's bounds were refused (bmin > bmax), NULL = not wanted */
 } QPGDeviceStep;
 int  qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io);
+/* The adjoint of the solved batch: gradients of a loss l(x*, y*) through the stored solutions, one launch, no second batch.
+ * Per member, with J = its active rows (each on its lower or its upper bound) and K = [[Q, A_J'], [A_J, 0]]: K [u; w] = [gx; gy_J] is solved by
+ * iterative refinement on a fresh factor of the member's regularised Schur complement, then
+ *   dq = -u;  dbmin_i = w_i on lower-active rows, dbmax_i = w_i on upper-active rows, 0 elsewhere;
+ *   dAx_k = -(y_i u_j + w_i x_j) for the k-th entry (i, j) the caller passed to qpg_batch_set_problem* (w_i = 0 outside J);
+ *   dQx_k = -(u_i x_j + u_j x_i) for a strictly lower entry, -u_i x_i for a diagonal one (a lower entry stands for both symmetric positions; upper
+ *   entries, which the engine ignores, and the padding up to nnzQ_max / nnzA_max get 0) -- the layout qpg_batch_update_Q_A takes.
+ * active_in = NULL: J by the engine's own test on the stored solution in scaled space (A x + y / sigma <= bmin: lower, >= bmax: upper; a row with
+ * bmin = bmax always, as lower); else -1 = lower, +1 = upper, 0 = inactive.  flag: 0 done; 1 the pass cap (200) was reached or the solve gave a
+ * non-finite value; 2 the member's status is not SOLVED / DUAL_TERMINATED.  With flag 1 or 2 every output of the member is zero.  resid = the last
+ * ||r||inf / (||K||inf ||z||inf + ||rhs||inf) in the engine's scaling (-1: non-finite), passes = corrections applied.  Entries beyond a sized member's
+ * own n / m are zero.  Synchronous, like the calls above; all arrays in device memory; inputs are only read.  The call may overwrite the factor slots
+ * and scratch vectors a finished solve leaves (the next solve rebuilds them); the iterates, stored solutions, penalties, statuses and counters stay.
+ * QPG_ERR_INVALID before qpg_batch_setup, while a solve is in progress (qpg_batch_iterate left a member unfinished), with gx = NULL and for an
+ * active_in entry outside {-1, 0, 1}; QPG_ERR_UNSUPPORTED for FACTORIZE_KKT batches, coop mode and nonconvex settings. */
+typedef struct {
+  const qpg_float *gx;        /* [B][n] dl/dx, required */
+  const qpg_float *gy;        /* [B][m] dl/dy or NULL (rows outside J are ignored: y_i = 0 there) */
+  const qpg_int   *active_in; /* [B][m] or NULL */
+  qpg_float       *dq;        /* out [B][n] */
+  qpg_float       *dbmin, *dbmax; /* out [B][m] */
+  qpg_float       *dQx, *dAx; /* out [B][nnzQ_max], [B][nnzA_max] */
+  qpg_int         *active_out; /* out [B][m]: the set used */
+  qpg_int         *flag;      /* out [B] */
+  qpg_float       *resid;     /* out [B] */
+  qpg_int         *passes;    /* out [B] */
+} QPGDeviceAdjoint;
+int  qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -60,6 +60,11 @@ class DeviceStep(C.Structure):
                 ("rejected", C.c_void_p)]
 
 
+class DeviceAdjoint(C.Structure):
+    """QPGDeviceAdjoint: the arrays of one qpg_batch_adjoint_device call, all addresses in device memory (0 = absent)."""
+    _fields_ = [(k, C.c_void_p) for k in ("gx", "gy", "active_in", "dq", "dbmin", "dbmax", "dQx", "dAx", "active_out", "flag", "resid", "passes")]
+
+
 class QpgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("qpalm_gfx950 error %d: %s" % (code, msg))
@@ -116,6 +121,8 @@ def load(path=None):
             getattr(L, f).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.qpg_batch_update_q_device.argtypes = [C.c_void_p, C.c_void_p]
         L.qpg_batch_step_device.argtypes = [C.c_void_p, C.POINTER(DeviceStep)]
+    if hasattr(L, "qpg_batch_adjoint_device"):   # (absent from older builds of the library that tools/evidence/adjoint_timing.py may be pointed at)
+        L.qpg_batch_adjoint_device.argtypes = [C.c_void_p, C.POINTER(DeviceAdjoint)]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -167,7 +174,7 @@ SYMBOLS = [
     "qpg_batch_begin_solve", "qpg_batch_get_info_all", "qpg_batch_get_stats_all", "qpg_ctx_hbm_copy_gbs", "qpg_ctx_hbm_read_gbs", "qpg_host_alloc", "qpg_host_free", "qpg_batch_set_problem_sized", "qpg_batch_set_problems",
     "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device", "qpg_batch_sparse_coop_info",
     "qpg_batch_update_bounds_device", "qpg_batch_update_q_device", "qpg_batch_warm_start_device", "qpg_batch_get_solution_device",
-    "qpg_batch_get_status_device", "qpg_batch_step_device", "qpg_batch_get_sparse_factor",
+    "qpg_batch_get_status_device", "qpg_batch_step_device", "qpg_batch_get_sparse_factor", "qpg_batch_adjoint_device",
 ]
 
 

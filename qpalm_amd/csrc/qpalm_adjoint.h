@@ -1,0 +1,229 @@
+/*
+ * qpalm_adjoint.h -- the adjoint of a solved QP: gradients of a loss l(x*, y*) with respect to q, bmin, bmax and the stored entries of Q and A
+ * (qpg_batch_adjoint_device, include/qpalm_gfx950.h).  No reference counterpart.
+ *
+ * At a fixed active set J (each active row on its lower or its upper bound) the solution satisfies K [x; y_J] = [-q; b_J] with
+ * K = [[Q, A_J'], [A_J, 0]], so for g = (dl/dx, dl/dy_J) the gradients follow from ONE solve K [u; w] = g:
+ *   dl/dq = -u,  dl/db_i = w_i on the bound row i sits on,  dl/dA_ij = -(y_i u_j + w_i x_j),  dl/dQ_ij = -(u_i x_j + u_j x_i)  (-u_i x_i on the diagonal).
+ * The engine works on the scaled problem (x~ = D^-1 x, y~ = c E^-1 y, Q~ = c D Q D, A~ = E A D): K~ [u~; w~] = [c D gx; E gy] with u = D u~,
+ * w = E w~ / c -- the transformations of x and y (dev_store_solution).
+ *
+ * K~ is solved by iterative refinement.  The preconditioner is the regularised system the iteration factorises all the time,
+ *   K_reg = [[Q~ + I / gamma, A~_J'], [A~_J, -Sigma_J^-1]]:   du = F^-1 (r1 + A~_J' Sigma_J r2),  dw = Sigma_J (A~_J du - r2),
+ * F = Q~ + I / gamma + A~_J' Sigma_J A~_J = one form_schur + dev_factor (sp_factor) on J with the member's own sigma and gamma; a pass is three
+ * SpMVs for the residual, one more and a triangular solve for du, one more for dw.  It stops with the correction of the first residual that has
+ * ||r||inf <= 4 eps (||K~||inf ||z||inf + ||rhs||inf) (a backward-stable solve), or at the pass cap (flag 1).
+ *
+ * Scratch: vectors a finished solve leaves behind and the next one rebuilds before it reads them (d, temp_n, delta_x, dphi, z, temp_m, delta_y,
+ * the line-search scratch, enter / leave) and the workgroup's factor slot.  The active flags form_schur / sp_factor read are saved and put back
+ * (update_sigma of a later solve may read them before its first Newton step).  x, y, the stored solution, sigma, gamma, Qx / Ax products and
+ * every scalar of the member stay as they are: the scalars are read into LDS and never written back.
+ */
+#ifndef QPALM_ADJOINT_H
+#define QPALM_ADJOINT_H
+
+QPD int adj_bad(double v) { return (qabs(v) <= 1.7976931348623157e308) ? 0 : 1; } /* NaN or infinite */
+
+template <int RPT>
+QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int slot, IterShared &I, char *lds) {
+  constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
+  const qpg_settings &st = *V.settings;
+  const QpArrays a = qp_arrays(V, b);
+  const int n = a.n, m = a.m, tid = threadIdx.x;
+  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  double *L = V.L + (size_t)slot * V.ld * V.nfac, *Dg = V.Dg + (size_t)slot * V.nfac;
+  __syncthreads();
+  if (tid == 0) I.s = V.sc[b]; /* a copy: the factorisation's timers land in it and go nowhere */
+  __syncthreads();
+  const int status = QP_UNIFORM(I.s.status);
+  int flag = (status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
+  int passes = 0;
+  double ratio = 0.0;
+  double *u = a.delta_x(), *w = a.temp_m();
+  int *sgn = a.enter(), *keep = a.leave(), *act = a.active();
+  if (flag == 0) {
+    const int scal = I.s.has_scaling, prox = qp_prox(st, I.s);
+    const double c = I.s.sc_c, gam = I.s.gamma;
+    double *xs = a.d(), *rhs1 = a.dphi(), *r1 = a.temp_n(), *rhs2 = a.z(), *r2 = a.delta_y(), *t = a.ls_delta();
+    /* ---- the scaled right-hand side and the active set ---- */
+    for (int j = tid; j < n; j += QP_T) {
+      const double g = io.gx[on + j];
+      xs[j] = scal ? a.sol_x()[j] * a.Dinv()[j] : a.sol_x()[j];
+      double r = g;
+      if (scal) { r = a.D()[j] * g; r *= c; }
+      rhs1[j] = r; u[j] = 0.0;
+    }
+    __syncthreads();
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { t[r] = s; });
+    __syncthreads();
+    for (int i = tid; i < m; i += QP_T) {
+      int sg;
+      if (io.active_in) { const int64_t v = io.active_in[om + i]; sg = (v < 0) ? -1 : ((v > 0) ? 1 : 0); }
+      else { /* set_active_constraints (newton.c:122-131) on the stored solution; an equality row counts as lower */
+        double yv = a.sol_y()[i];
+        if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
+        const double axys = t[i] + 1 * (yv * a.sigma_inv()[i]);
+        const double lo = a.bmin()[i], hi = a.bmax()[i];
+        sg = (lo == hi || axys <= lo) ? -1 : ((axys >= hi) ? 1 : 0);
+      }
+      sgn[i] = sg; keep[i] = act[i]; act[i] = (sg != 0) ? 1 : 0;
+      const double g = (io.gy && sg) ? io.gy[om + i] : 0.0;
+      rhs2[i] = scal ? a.E()[i] * g : g;
+      w[i] = 0.0;
+    }
+    __syncthreads();
+    /* ---- ||K~||inf (largest absolute row sum) and ||rhs||inf ---- */
+    double vm[2] = {0.0, 0.0}, vs[1] = {0.0};
+    for (int j = tid; j < n; j += QP_T) {
+      double s = 0.0;
+      for (int k = a.Qfp()[j]; k < a.Qfp()[j + 1]; k++) s += qabs(a.Qfx()[k]);
+      for (int k = a.Ap()[j]; k < a.Ap()[j + 1]; k++) if (sgn[a.Ai()[k]]) s += qabs(a.Ax()[k]);
+      vm[0] = qmax(vm[0], s);
+      vm[1] = qmax(vm[1], qabs(rhs1[j]));
+    }
+    for (int i = tid; i < m; i += QP_T) {
+      if (!sgn[i]) continue;
+      double s = 0.0;
+      for (int k = a.Atp()[i]; k < a.Atp()[i + 1]; k++) s += qabs(a.Atx()[k]);
+      vm[0] = qmax(vm[0], s);
+      vm[1] = qmax(vm[1], qabs(rhs2[i]));
+    }
+    block_reduce<2, 0>(I.S, vm, vs);
+    const double normK = vm[0], rhsn = vm[1];
+    /* ---- F = Q~ (+ I / gamma) + A~_J' Sigma_J A~_J, factorised afresh: the slot may hold another member's factor, or this member's for another set ---- */
+    if constexpr (SPARSE) {
+      const SpArrays SP = sp_arrays(V, b, slot, Dg, lds);
+      if (QP_CALL_BLOCK()) sp_factor(V, b, n, SP, true, prox != 0, gam);
+    } else {
+      form_schur(V, b, n, L, false, true, prox != 0, gam, I.S, lds);
+      dev_factor<RPT>(V, n, L, Dg, lds, I.s.ticks_dbg);
+    }
+    /* ---- refinement on K~ z = rhs, z = [u; w] ---- */
+    for (int pass = 0;; pass++) {
+      __syncthreads();
+      spmv_rows<8>(n, a.Qfp(), a.Qfi(), a.Qfx(), (const double *)u, [&](int r, double s) { r1[r] = rhs1[r] - s; });
+      spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)u, [&](int r, double s) { r2[r] = sgn[r] ? rhs2[r] - s : 0.0; });
+      __syncthreads();
+      spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)w, [&](int r, double s) { r1[r] = r1[r] - s; });
+      __syncthreads();
+      vm[0] = 0.0; vm[1] = 0.0; vs[0] = 0.0;
+      for (int j = tid; j < n; j += QP_T) {
+        vm[0] = qmax(vm[0], qabs(r1[j])); vm[1] = qmax(vm[1], qabs(u[j]));
+        vs[0] += (double)(adj_bad(r1[j]) | adj_bad(u[j]));
+      }
+      for (int i = tid; i < m; i += QP_T) {
+        vm[0] = qmax(vm[0], qabs(r2[i])); vm[1] = qmax(vm[1], qabs(w[i]));
+        vs[0] += (double)(adj_bad(r2[i]) | adj_bad(w[i]));
+      }
+      block_reduce<2, 1>(I.S, vm, vs);
+      const double den = normK * vm[1] + rhsn;
+      /* (the same values in every lane: scalar branches) */
+      const int bad = QP_UNIFORM((int)(vs[0] != 0.0)), conv = QP_UNIFORM((int)(vm[0] <= 4.0 * 2.220446049250313e-16 * den));
+      passes = pass;
+      ratio = bad ? -1.0 : ((den > 0.0) ? vm[0] / den : 0.0);
+      if (bad) { flag = 1; break; }
+      if (!conv && pass >= io.max_pass) { flag = 1; break; }
+      if (vm[0] == 0.0) break;
+      /* the correction this residual gives is applied in either case: the iteration converges linearly, so the iterate whose residual first meets the
+       * bound sits AT the bound, and its correction is what takes the error down to the rounding level of the solve (`passes` counts it) */
+      passes = pass + 1;
+      for (int i = tid; i < m; i += QP_T) t[i] = sgn[i] ? a.sigma()[i] * r2[i] : 0.0;
+      __syncthreads();
+      spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)t, [&](int r, double s) { xs[r] = r1[r] + s; });
+      __syncthreads();
+      if constexpr (SPARSE) { if (QP_CALL_BLOCK()) sp_solve(n, sp_arrays(V, b, slot, Dg, lds), xs); }
+      else { if (QP_CALL_BLOCK()) dense_solve(L, Dg, n, V.ld, xs, lds, V.lds_bytes); }
+      __syncthreads();
+      spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { if (sgn[r]) w[r] = w[r] + a.sigma()[r] * (s - r2[r]); });
+      for (int j = tid; j < n; j += QP_T) u[j] = u[j] + xs[j];
+      if (conv) break;
+    }
+    __syncthreads();
+    /* back to the caller's scaling; the flags of the active set go back where the next solve expects them */
+    for (int j = tid; j < n; j += QP_T) { u[j] = (flag == 0) ? (scal ? a.D()[j] * u[j] : u[j]) : 0.0; xs[j] = 0.0; }
+    for (int i = tid; i < m; i += QP_T) {
+      double wv = w[i];
+      if (scal) { wv = wv * I.s.sc_cinv; wv = wv * a.E()[i]; }
+      w[i] = (flag == 0) ? wv : 0.0;
+      act[i] = keep[i];
+    }
+    __syncthreads();
+  }
+  /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros ---- */
+  const bool ok = (flag == 0);
+  if (io.dq) for (int j = tid; j < V.n; j += QP_T) io.dq[on + j] = (ok && j < n) ? -u[j] : 0.0;
+  for (int i = tid; i < V.m; i += QP_T) {
+    const int sg = (flag != 2 && i < m) ? sgn[i] : 0;
+    const double wv = (ok && i < m) ? w[i] : 0.0;
+    if (io.dbmin) io.dbmin[om + i] = (sg < 0) ? wv : 0.0;
+    if (io.dbmax) io.dbmax[om + i] = (sg > 0) ? wv : 0.0;
+    if (io.active_out) io.active_out[om + i] = sg;
+  }
+  if (tid == 0) {
+    if (io.flag) io.flag[b] = flag;
+    if (io.resid) io.resid[b] = ratio;
+    if (io.passes) io.passes[b] = passes;
+  }
+  /* ---- the per-entry gradients, in the order qpg_batch_update_Q_A takes its values (k_update_Q_A's maps, the other way round); eight lanes per column ---- */
+  if (io.dAx) {
+    double *o = io.dAx + (size_t)b * io.strideA;
+    for (int64_t k = tid; k < io.strideA; k += QP_T) o[k] = 0.0;
+    __syncthreads();
+    if (ok) {
+      const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1;
+      const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr;
+      for (int j = tid >> 3; j < n; j += QP_T >> 3) {
+        const double uj = u[j], xj = a.sol_x()[j];
+        for (int k = a.Ap()[j] + (tid & 7); k < a.Ap()[j + 1]; k += 8) {
+          const int i = a.Ai()[k];
+          o[sameA ? k : mA[k]] = -(a.sol_y()[i] * uj + w[i] * xj);
+        }
+      }
+    }
+  }
+  if (io.dQx) {
+    double *o = io.dQx + (size_t)b * io.strideQ;
+    for (int64_t k = tid; k < io.strideQ; k += QP_T) o[k] = 0.0;
+    __syncthreads();
+    if (ok) {
+      const int sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
+      const int32_t *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
+      for (int j = tid >> 3; j < n; j += QP_T >> 3) {
+        const double uj = u[j], xj = a.sol_x()[j];
+        for (int k = a.Qp()[j] + (tid & 7); k < a.Qp()[j + 1]; k += 8) {
+          const int i = a.Qi()[k]; /* i >= j: the stored entry stands for both symmetric positions */
+          o[sameQ ? k : mQ[k]] = (i == j) ? -(uj * xj) : -(u[i] * xj + uj * a.sol_x()[i]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+/* One workgroup per factor slot; the members come off the work queue (V.queue[0], zeroed by the host) as in k_solve, so B > slots works.
+ * RPT = QPG_RPT_SPARSE: the sparse factor (sp_factor / sp_solve); any other value: the dense panel. */
+template <int RPT>
+__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_adjoint_args io) {
+  __shared__ IterShared I;
+  char *lds = QP_DYN_LDS();
+  while (true) {
+    __syncthreads();
+    if (threadIdx.x == 0) I.S.ibc[0] = atomicAdd(V.queue, 1);
+    __syncthreads();
+    const int b = QP_UNIFORM(I.S.ibc[0]);
+    if (b >= V.B) break;
+    dev_adjoint<RPT>(V, io, b, blockIdx.x, I, lds);
+  }
+}
+
+/* active_in ([B][m] of the batch's strides) may only hold -1, 0, 1 within a member's own rows: *bad = 1 otherwise */
+__global__ __launch_bounds__(QP_T) void k_adjoint_check(qpg_view V, const int64_t *active_in, int *bad) {
+  const size_t total = (size_t)V.B * V.m;
+  for (size_t e = (size_t)blockIdx.x * QP_T + threadIdx.x; e < total; e += (size_t)gridDim.x * QP_T) {
+    const int b = (int)(e / V.m), i = (int)(e % V.m);
+    const int64_t v = active_in[e];
+    if (i < (V.mq ? V.mq[b] : V.m) && (v < -1 || v > 1)) *bad = 1;
+  }
+}
+
+#endif

@@ -1863,6 +1863,30 @@ extern "C" int qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q) {
   return api_ok();
 }
 
+/* The maps between the device's order of the entries of A / Q and the caller's (qpg_batch::map_A / map_Q), in device memory: uploaded at the first call
+ * that needs them.  All three stay NULL when every member was given in the device's order. */
+static int value_maps_device(qpg_batch *bt, int32_t **mapA_d, int32_t **mapQ_d, int32_t **same_d) {
+  const size_t B = bt->B, zA = bt->nnzA, zQ = bt->nnzQ;
+  *mapA_d = *mapQ_d = *same_d = nullptr;
+  bool any_map = false;
+  for (size_t b = 0; b < B && !any_map; b++) any_map = !bt->map_A[b].empty() || !bt->map_Q[b].empty();
+  if (!any_map) return QPG_OK;
+  const size_t oQ = align_up(B * zA * 4, 256), oS = oQ + align_up(B * zQ * 4, 256), bytes = oS + B * 2 * 4;
+  if (!bt->val_maps_d && RT_MALLOC(&bt->val_maps_d, bytes) != 0) { bt->val_maps_d = nullptr; return fail(QPG_ERR_ALLOC, "device allocation failed (value maps)"); }
+  *mapA_d = (int32_t *)bt->val_maps_d; *mapQ_d = (int32_t *)((char *)bt->val_maps_d + oQ); *same_d = (int32_t *)((char *)bt->val_maps_d + oS);
+  if (!bt->val_maps_current) {
+    std::vector<int32_t> same(B * 2);
+    for (size_t b = 0; b < B; b++) {
+      same[2 * b] = bt->map_A[b].empty() ? 1 : 0; same[2 * b + 1] = bt->map_Q[b].empty() ? 1 : 0;
+      if (!same[2 * b]) RT_MEMCPY_H2D(*mapA_d + b * zA, bt->map_A[b].data(), bt->map_A[b].size() * 4);
+      if (!same[2 * b + 1]) RT_MEMCPY_H2D(*mapQ_d + b * zQ, bt->map_Q[b].data(), bt->map_Q[b].size() * 4);
+    }
+    RT_MEMCPY_H2D(*same_d, same.data(), same.size() * 4);
+    bt->val_maps_current = true;
+  }
+  return QPG_OK;
+}
+
 /* qpalm_update_Q_A for every member: new values of Q and A on the patterns the batch was set up with.  Afterwards the batch is what qpg_batch_setup
  * would leave for these values, the latest accepted raw q / bounds and the current settings -- without the host-side conversion, the symbolic
  * analysis of the sparse factors, the pattern uploads or a new arena.  Kept: the arena, the factor and LD_Q slots, nq / mq, the settings block, the
@@ -1871,25 +1895,9 @@ extern "C" int qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q) {
  * order of qpg_batch_set_problem*; strideQ / strideA: doubles between two members in them. */
 static int update_Q_A_device(qpg_batch *bt, const double *dQx, size_t strideQ, const double *dAx, size_t strideA) {
   qpg_view &V = bt->V;
-  const size_t B = bt->B, n = bt->n, m = bt->m, zA = bt->nnzA, zQ = bt->nnzQ;
+  const size_t B = bt->B, n = bt->n, m = bt->m;
   int32_t *mapA_d = nullptr, *mapQ_d = nullptr, *same_d = nullptr;
-  bool any_map = false;
-  for (size_t b = 0; b < B && !any_map; b++) any_map = !bt->map_A[b].empty() || !bt->map_Q[b].empty();
-  if (any_map) {
-    const size_t oQ = align_up(B * zA * 4, 256), oS = oQ + align_up(B * zQ * 4, 256), bytes = oS + B * 2 * 4;
-    if (!bt->val_maps_d && RT_MALLOC(&bt->val_maps_d, bytes) != 0) { bt->val_maps_d = nullptr; return fail(QPG_ERR_ALLOC, "device allocation failed (value maps)"); }
-    mapA_d = (int32_t *)bt->val_maps_d; mapQ_d = (int32_t *)((char *)bt->val_maps_d + oQ); same_d = (int32_t *)((char *)bt->val_maps_d + oS);
-    if (!bt->val_maps_current) {
-      std::vector<int32_t> same(B * 2);
-      for (size_t b = 0; b < B; b++) {
-        same[2 * b] = bt->map_A[b].empty() ? 1 : 0; same[2 * b + 1] = bt->map_Q[b].empty() ? 1 : 0;
-        if (!same[2 * b]) RT_MEMCPY_H2D(mapA_d + b * zA, bt->map_A[b].data(), bt->map_A[b].size() * 4);
-        if (!same[2 * b + 1]) RT_MEMCPY_H2D(mapQ_d + b * zQ, bt->map_Q[b].data(), bt->map_Q[b].size() * 4);
-      }
-      RT_MEMCPY_H2D(same_d, same.data(), same.size() * 4);
-      bt->val_maps_current = true;
-    }
-  }
+  { const int rcm = value_maps_device(bt, &mapA_d, &mapQ_d, &same_d); if (rcm != QPG_OK) return rcm; }
   /* the raw q and bounds a fresh setup would upload */
   if (bt->raw_cur == 1) raw_need_host(bt); /* the device forms of the updates wrote last: their record comes over (one transfer) */
   const bool rec = !bt->raw_h.empty();
@@ -1947,6 +1955,52 @@ extern "C" int qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io) {
   if ((rc = qpg_batch_get_solution_device(bt, io->x, io->y)) != QPG_OK) return rc;
   if ((rc = qpg_batch_get_status_device(bt, io->status_val, io->iter)) != QPG_OK) return rc;
   if (refused) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
+  return api_ok();
+}
+
+/* The adjoint of the solved batch (include/qpalm_gfx950.h; the kernel: qpalm_adjoint.h).  One launch of one workgroup per factor slot; the members come
+ * off the work queue.  Pass cap of the refinement: 200 (a pass contracts the error by about 1 / (1 + sigma lambda), lambda the eigenvalues of
+ * A_J Q^-1 A_J': sixteen digits in a handful of passes at the penalties a finished solve holds, and a member that needs more than 200 is flagged). */
+#define QPG_ADJOINT_MAX_PASS 200
+extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) {
+  NEED_SETUP(bt, "qpg_batch_adjoint_device");
+  if (!io || !io->gx) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: gx is NULL");
+  if (bt->kkt) return fail(QPG_ERR_UNSUPPORTED, bt->sparse ? "qpg_batch_adjoint_device: not available for FACTORIZE_KKT batches (sparse_kkt)" : "qpg_batch_adjoint_device: not available for FACTORIZE_KKT batches (dense KKT panel)");
+  if (bt->settings.nonconvex) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_adjoint_device: not available with nonconvex = 1");
+  if (coop_wanted(bt) || sparse_coop_wanted(bt)) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_adjoint_device: not available in coop mode (one QP on many workgroups)");
+  {
+    std::vector<qpg_scalars> sc(bt->B);
+    RT_MEMCPY_D2H(sc.data(), bt->V.sc, sc.size() * sizeof(qpg_scalars));
+    for (auto &s : sc) if (s.in_solve) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: a solve is in progress (qpg_batch_iterate left a member unfinished)");
+  }
+  int *word = (int *)bt->V.queue; /* [0]: the work-queue head */
+  if (io->active_in && bt->m > 0) {
+    int *bad_d = word + 1; /* (a free word of the queue block: k_solve uses [0] and [64 ..)) */
+    RT_MEMSET(bad_d, 0, sizeof(int));
+    BT_LAUNCH(bt, k_adjoint_check, (int)std::min<size_t>(((size_t)bt->B * bt->m + bt->threads - 1) / bt->threads, 1024), 0, bt->V, (const int64_t *)io->active_in, bad_d);
+    if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint_check failed: " + std::string(RT_LAST_ERROR()));
+    int bad = 0;
+    RT_MEMCPY_D2H(&bad, bad_d, sizeof(int));
+    if (bad) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: active_in holds a value other than -1, 0, 1");
+  }
+  qpg_adjoint_args ar;
+  memset(&ar, 0, sizeof(ar));
+  ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)io->active_in;
+  ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
+  ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
+  ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS;
+  if (io->dQx || io->dAx) {
+    int32_t *mapA_d, *mapQ_d, *same_d;
+    const int rcm = value_maps_device(bt, &mapA_d, &mapQ_d, &same_d);
+    if (rcm != QPG_OK) return rcm;
+    ar.mapA = mapA_d; ar.mapQ = mapQ_d; ar.same = same_d;
+  }
+  RT_MEMSET(word, 0, sizeof(int));
+  const int grid = std::min(bt->B, bt->nslots);
+  const size_t shm = (size_t)bt->lds_bytes;
+  if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
+  else BT_LAUNCH(bt, k_adjoint<1>, grid, shm, bt->V, ar);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
 }
 

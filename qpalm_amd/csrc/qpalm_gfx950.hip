@@ -37,6 +37,7 @@ namespace qp512 {
 #undef QPALM_KKT_H
 #undef QPALM_SPARSE_H
 #undef QPALM_SPARSE_KKT_H
+#undef QPALM_ADJOINT_H
 #define QP_T 256
 #define QP_KSEL(RPT) 8
 #define QP_FKC 16
@@ -58,6 +59,7 @@ static_assert(sizeof(UpdownLds<1, 8>) <= 38912 && sizeof(FactorLds) + sizeof(Fac
 #undef QPALM_KKT_H
 #undef QPALM_SPARSE_H
 #undef QPALM_SPARSE_KKT_H
+#undef QPALM_ADJOINT_H
 #ifndef QP_TINY_K
 #define QP_TINY_K 8 /* ranks per update sweep of the 128-thread instance */
 #endif

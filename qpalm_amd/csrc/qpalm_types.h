@@ -151,6 +151,20 @@ typedef struct {
                      (k_queue_order; identity before the first solve), so that the last QPs of a launch are short ones.  NULL: index order */
 } qpg_view;
 
+/* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint (include/qpalm_gfx950.h; NULL = absent) and the
+ * maps of k_update_Q_A from the device's order of the entries of Q / A back to the caller's (NULL: the same order everywhere) */
+typedef struct {
+  const double *gx, *gy;      /* [B][n], [B][m] */
+  const int64_t *active_in;   /* [B][m]: -1 lower, +1 upper, 0 inactive */
+  double *dq, *dbmin, *dbmax; /* [B][n], [B][m], [B][m] */
+  double *dQx, *dAx;          /* [B][strideQ], [B][strideA] in the caller's order of the entries */
+  int64_t *active_out, *flag, *passes; /* [B][m], [B], [B] */
+  double *resid;              /* [B] */
+  const int32_t *mapQ, *mapA, *same;
+  int64_t strideQ, strideA;
+  int32_t max_pass;           /* pass cap of the refinement */
+} qpg_adjoint_args;
+
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */
 #define QPG_KMAX 16 /* ranks per sweep of the large-factor and coop-mode sweeps */
 #define QPG_KWST 32 /* dense update vectors the staging area of a slot holds = most ranks per sweep of dense_updown */

@@ -97,6 +97,7 @@ class QpalmBatch:
         nnzQ = max(int(p.Qp[-1]) for p in problems)
         self.nnzA, self.nnzQ = nnzA, nnzQ   # row lengths of the arrays update_Q_A takes
         self.settings = settings if settings is not None else ctx.default_settings()
+        self.epoch = 0   # counts the calls that change what adjoint_device differentiates (solves, warm starts, updates): torch_layer checks it
         h = C.c_void_p()
         import time
         t0 = time.perf_counter()
@@ -128,18 +129,22 @@ class QpalmBatch:
 
     # -- qpalm.h API ---------------------------------------------------------------------------
     def warm_start(self, x=None, y=None):
+        self.epoch += 1
         xs = f64(x).reshape(self.B, self.n) if x is not None else None
         ys = f64(y).reshape(self.B, self.m) if y is not None else None
         self._check(self.L.qpg_batch_warm_start(self.h, fptr(xs) if xs is not None else None, fptr(ys) if ys is not None else None))
 
     def warm_start_last(self):
         """qpalm_warm_start of every QP with its own last solution, device-resident (the MPC receding-horizon step)."""
+        self.epoch += 1
         self._check(self.L.qpg_batch_warm_start_last(self.h))
 
     def solve(self):
+        self.epoch += 1
         self._check(self.L.qpg_batch_solve(self.h))
 
     def iterate(self, k=1):
+        self.epoch += 1
         self._check(self.L.qpg_batch_iterate(self.h, int(k)))
 
     def last_solve_ms(self):
@@ -193,17 +198,20 @@ class QpalmBatch:
         return int(c.value)
 
     def update_settings(self, s):
+        self.epoch += 1
         rc = self.L.qpg_batch_update_settings(self.h, C.byref(s))
         if rc == 0:
             self.settings = s
         return rc
 
     def update_bounds(self, bmin=None, bmax=None):
+        self.epoch += 1
         a = f64(bmin).reshape(self.B, self.m) if bmin is not None else None
         b = f64(bmax).reshape(self.B, self.m) if bmax is not None else None
         return self.L.qpg_batch_update_bounds(self.h, fptr(a) if a is not None else None, fptr(b) if b is not None else None)
 
     def update_q(self, q):
+        self.epoch += 1
         q = f64(q).reshape(self.B, self.n)
         self._check(self.L.qpg_batch_update_q(self.h, fptr(q)))
 
@@ -228,11 +236,13 @@ class QpalmBatch:
         """qpalm_update_Q_A: new values of Q and A on the patterns the batch was set up with, each member's in the order of the Qx / Ax its problem was
         given with.  [B][nnzQ_max] / [B][nnzA_max] arrays, or lists of per-member arrays.  The batch is then what a fresh setup with these values, the
         latest q / bounds and the current settings would be; the stored solutions stay (warm_start_last)."""
+        self.epoch += 1
         q, a = self._padded(Qx, self.nnzQ), self._padded(Ax, self.nnzA)
         self._check(self.L.qpg_batch_update_Q_A(self.h, fptr(q), fptr(a)))
 
     def update_Q_A_device(self, ptr_Qx, ptr_Ax):
         """the same from device memory: raw addresses of [B][nnzQ_max] / [B][nnzA_max] float64 arrays (e.g. torch tensors' data_ptr())"""
+        self.epoch += 1
         self._check(self.L.qpg_batch_update_Q_A_device(self.h, C.c_void_p(int(ptr_Qx)), C.c_void_p(int(ptr_Ax))))
 
     # -- the per-step calls on arrays in device memory ---------------------------------------------------
@@ -275,16 +285,19 @@ class QpalmBatch:
 
     def update_bounds_device(self, bmin=None, bmax=None):
         """update_bounds from [B][m] float64 arrays in device memory (torch tensors or raw addresses); returns the code like update_bounds"""
+        self.epoch += 1
         a, b = self._dev_args((bmin, (self.B, self.m), "bmin", "float64"), (bmax, (self.B, self.m), "bmax", "float64"))
         return self.L.qpg_batch_update_bounds_device(self.h, a, b)
 
     def update_q_device(self, q):
+        self.epoch += 1
         if q is None:
             raise ValueError("q: expected a torch tensor or a raw address")
         a, = self._dev_args((q, (self.B, self.n), "q", "float64"))
         self._check(self.L.qpg_batch_update_q_device(self.h, a))
 
     def warm_start_device(self, x=None, y=None):
+        self.epoch += 1
         a, b = self._dev_args((x, (self.B, self.n), "x", "float64"), (y, (self.B, self.m), "y", "float64"))
         self._check(self.L.qpg_batch_warm_start_device(self.h, a, b))
 
@@ -310,6 +323,7 @@ class QpalmBatch:
         torch tensors on the context's device or raw addresses.  out: a dict with any of the keys x, y, status_val, iter, rejected (absent or None =
         not wanted); without it all five are allocated.  Returns (rc, out): rc = 0, or -2 (QPG_ERR_INVALID) when some member's bounds were refused --
         the step has run all the same, that member on its old bounds, and out["rejected"] says which."""
+        self.epoch += 1
         if out is None:
             out = dict(x=self._empty((self.B, self.n)), y=self._empty((self.B, self.m)), status_val=self._empty((self.B,), "int64"),
                        iter=self._empty((self.B,), "int64"), rejected=self._empty((self.B,), "int64"))
@@ -338,6 +352,32 @@ class QpalmBatch:
         if rc not in (0, -2):
             self._check(rc)
         return rc, out
+
+    ADJOINT_OUT = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
+
+    def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None):
+        """Gradients of a loss through the stored solutions (qpg_batch_adjoint_device): gx = dl/dx [B][n], gy = dl/dy [B][m] or None, active = the active
+        set to differentiate at ([B][m] int64: -1 lower, +1 upper, 0 inactive) or None for the engine's own test on the stored solution.  All arrays
+        are torch tensors on the context's device or raw addresses.  want: which outputs to compute, among dq [B][n], dbmin / dbmax [B][m],
+        dQx [B][nnzQ_max], dAx [B][nnzA_max] (the layout update_Q_A takes), active [B][m] int64 (the set used), flag [B] int64 (0 done, 1 pass cap /
+        non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses to fill instead (then `want` is ignored).
+        Returns the dict."""
+        nB, n, m = self.B, self.n, self.m
+        shapes = dict(dq=((nB, n), "float64"), dbmin=((nB, m), "float64"), dbmax=((nB, m), "float64"), dQx=((nB, self.nnzQ), "float64"),
+                      dAx=((nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
+                      passes=((nB,), "int64"))
+        unknown = set(out if out is not None else want) - set(shapes)
+        if unknown:
+            raise ValueError("adjoint_device: unknown outputs %r" % sorted(unknown))
+        if gx is None:
+            raise ValueError("gx: expected a torch tensor or a raw address")
+        if out is None:
+            out = {k: self._empty(*shapes[k]) for k in want}
+        a = self._dev_args((gx, (nB, n), "gx", "float64"), (gy, (nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
+                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
+        io = capi.DeviceAdjoint(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11])
+        self._check(self.L.qpg_batch_adjoint_device(self.h, C.byref(io)))
+        return out
 
     # -- results --------------------------------------------------------------------------------
     def info(self, b=0):
@@ -374,6 +414,7 @@ class QpalmBatch:
         return out
 
     def begin_solve(self):
+        self.epoch += 1
         self._check(self.L.qpg_batch_begin_solve(self.h))
 
     def solution_of(self, k):

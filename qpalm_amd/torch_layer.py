@@ -1,0 +1,57 @@
+"""The batched QP as a differentiable torch layer: forward = one step on the device (QpalmBatch.step_device, after update_Q_A_device when Q / A values
+are given), backward = the adjoint of the solved batch (QpalmBatch.adjoint_device).  This file only passes tensors through: the solve and the gradients
+are the HIP kernels behind include/qpalm_gfx950.h.
+
+    layer = QPLayer(batch)                       # a set-up QpalmBatch; its patterns, sizes and settings stay
+    x, y, status = layer(q, bmin, bmax)          # [B][n], [B][m] float64 tensors on the batch's device (None = unchanged), optionally Qx=, Ax=
+    loss(x, y).backward()                        # q.grad, bmin.grad, bmax.grad (Qx.grad, Ax.grad)
+
+The gradient is that of the active set at the solution; members that did not end SOLVED / DUAL_TERMINATED, or whose adjoint solve
+was flagged, get zero gradients -- `layer.last_adjoint` keeps the flags, residuals and pass counts of the latest backward call.
+
+backward() differentiates the state the batch holds, so it must run before the batch is solved, warm-started or updated again (by this layer or directly):
+the batch counts those calls (`QpalmBatch.epoch`) and a backward() that comes too late raises RuntimeError instead of returning another solve's gradients."""
+import torch
+
+
+class _QPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, layer, q, bmin, bmax, Qx, Ax):
+        bt = layer.batch
+        if (Qx is None) != (Ax is None):
+            raise ValueError("Qx and Ax: give both or neither (update_Q_A takes both)")
+        if Qx is not None:
+            a, b = bt._dev_args((Qx.detach(), (bt.B, bt.nnzQ), "Qx", "float64"), (Ax.detach(), (bt.B, bt.nnzA), "Ax", "float64"))
+            bt.update_Q_A_device(a.value, b.value)
+        det = lambda t: None if t is None else t.detach()
+        rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm)
+        if rc != 0:
+            raise ValueError("QPLayer: some member's bounds were refused (bmin > bmax): %r" % out["rejected"].nonzero().flatten().tolist())
+        fctx.layer, fctx.epoch = layer, bt.epoch
+        fctx.mark_non_differentiable(out["status_val"])
+        return out["x"], out["y"], out["status_val"]
+
+    @staticmethod
+    def backward(fctx, gx, gy, _gs):
+        layer = fctx.layer
+        bt = layer.batch
+        if bt.epoch != fctx.epoch:
+            raise RuntimeError("QPLayer.backward: the batch was solved or updated again after this forward pass; its gradients are gone")
+        need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
+        want = tuple(k for k, v in need.items() if v) + ("flag", "resid", "passes")
+        gx = bt._empty((bt.B, bt.n)).zero_() if gx is None else gx.contiguous()
+        out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), want=want)
+        layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
+        return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx"))
+
+
+class QPLayer(torch.nn.Module):
+    """x*(q, bmin, bmax[, Qx, Ax]) of a set-up QpalmBatch as a torch module.  warm: the warm start of every forward step, as step_device takes it
+    (None = cold, "last" = every member's previous solution)."""
+
+    def __init__(self, batch, warm=None):
+        super().__init__()
+        self.batch, self.warm, self.last_adjoint = batch, warm, None
+
+    def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None):
+        return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax)
