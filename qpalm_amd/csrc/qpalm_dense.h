@@ -312,19 +312,15 @@ template <int R> QPD void qp_store_rows(qp_gdouble *p, const double *v) {
 }
 #endif
 /* the update sweep's panel traffic with the non-temporal hint (an entry is read once and written once per sweep, the next sweep
- * is ~1 ms and 4 GB of other QPs' panels away): QP_NT_PANEL 1 = the sweep's stores, 2 = its loads and stores, 3 = also the panel reads
- * of the triangular solves, 4 = also those of the factorisation's panel update.  Measured in DESIGN section 7. */
-#ifndef QP_NT_PANEL
-#define QP_NT_PANEL 3
-#endif
+ * is ~1 ms and 4 GB of other QPs' panels away): the sweep's loads and stores and the panel reads of the triangular solves (QP_LDNT);
+ * the panel re-read of the factorisation's update stays a plain load.  Measured in DESIGN section 7. */
 #ifdef QPALM_EMU
 #define qp_load_rows_nt qp_load_rows
 #define qp_store_rows_nt qp_store_rows
-#define QP_LDNT(lvl, p) (*(p))
+#define QP_LDNT(p) (*(p))
 #else
-#define QP_LDNT(lvl, p) ((QP_NT_PANEL >= (lvl)) ? __builtin_nontemporal_load(p) : *(p)) /* a streaming read of the panel (level = which phase, see QP_NT_PANEL) */
+#define QP_LDNT(p) __builtin_nontemporal_load(p) /* a streaming read of the panel */
 template <int R> QPD void qp_load_rows_nt(const qp_gdouble *p, double *v) {
-  if (QP_NT_PANEL < 2) { qp_load_rows<R>(p, v); return; }
   if (R % 2 == 0) {
 #pragma unroll
     for (int k = 0; k < R; k += 2) { const qp_double2 t = __builtin_nontemporal_load((const qp_gdouble2 *)(p + k)); v[k] = t.x; v[k + 1] = t.y; }
@@ -334,7 +330,6 @@ template <int R> QPD void qp_load_rows_nt(const qp_gdouble *p, double *v) {
   }
 }
 template <int R> QPD void qp_store_rows_nt(qp_gdouble *p, const double *v) {
-  if (QP_NT_PANEL < 1) { qp_store_rows<R>(p, v); return; }
   if (R % 2 == 0) {
 #pragma unroll
     for (int k = 0; k < R; k += 2) { qp_double2 t; t.x = v[k]; t.y = v[k + 1]; __builtin_nontemporal_store(t, (qp_gdouble2 *)(p + k)); }
@@ -370,9 +365,6 @@ struct FactorLds {
  *  - Block row i of the MFMA A operand is column J + NCT*i + ct of the super-block (ct = column tile), so the NCT tile
  *    values of a lane are adjacent in LDS (16-byte reads).  Which MFMA lane handles which entry does not change any
  *    entry's sum: k ascending, one fma per k, as before. */
-#ifndef QP_NI_FGEMM
-#define QP_NI_FGEMM QPNI
-#endif
 #ifndef QP_FKC
 #define QP_FKC 32 /* columns per staged chunk (J and the k ranges are multiples of it); 16 in the 256-thread instance (LDS budget) */
 #endif
@@ -449,8 +441,7 @@ QPD void factor_panel_update_body(double *L_, const double *Dg_, char *stage_, i
   constexpr int S = QP_FST, NH = QP_FKC / 4;
   static_assert(NH % S == 0, "QP_FST must divide QP_FKC / 4");
   double rb[S][NTJ];
-  auto loadb = [&](const int st, const int k) QP_ALWAYS_INLINE { /* the panel re-read of the left-looking update */
-    if (QP_NT_PANEL >= 4) qp_load_rows_nt<NTJ>(L + (size_t)(k + l4) * ld + rowb, rb[st]); else qp_load_rows<NTJ>(L + (size_t)(k + l4) * ld + rowb, rb[st]); };
+  auto loadb = [&](const int st, const int k) QP_ALWAYS_INLINE { qp_load_rows<NTJ>(L + (size_t)(k + l4) * ld + rowb, rb[st]); }; /* the panel re-read of the left-looking update */
   auto mma = [&](const int st, const int buf, const int h) QP_ALWAYS_INLINE {
     double pa[NCT];
 #pragma unroll
@@ -514,18 +505,16 @@ QPD bool factor_solve_fits(const int n, const int lds_bytes) { return QP_FACTOR_
 
 /* the panel update as a real call (the multi-workgroup factorisation, co_factor_trailing) */
 template <int NTJ, int NCT>
-QP_NI_FGEMM void factor_panel_update(double *L_, const double *Dg_, char *stage_, int n_, int ld_, int J_, int tbase_, int k0_, int k1_) {
+QPNI void factor_panel_update(double *L_, const double *Dg_, char *stage_, int n_, int ld_, int J_, int tbase_, int k0_, int k1_) {
   factor_panel_update_body<NTJ, NCT>(L_, Dg_, stage_, n_, ld_, J_, tbase_, k0_, k1_);
 }
 
 /* Step (3) of dense_factor: one row per thread, the row's 32 panel entries live
- * in registers (64 VGPRs), L and 1/D of the diagonal block come as LDS broadcasts. */
-#ifndef QP_NI_FROWS
-#define QP_NI_FROWS QPD /* inline: dense_factor keeps ONE register frame per factorisation (profiles/factor_scratch) */
-#endif
+ * in registers (64 VGPRs), L and 1/D of the diagonal block come as LDS broadcasts.
+ * Inline: dense_factor keeps ONE register frame per factorisation (profiles/factor_scratch). */
 /* fuse_ != 0: the forward substitution of the solve that follows rides along (dense_factor, fs): y_i <- fma(-l_ic, y_c, y_i), c ascending,
  * with the l_ic just stored and the block's y_c that factor_diag_block left in LDS -- row i on thread (i - J - jb) % QP_T, as in dense_solve */
-QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const int ld_, const int J_, const int jb_, const int fuse_ = 0) {
+QPD void factor_panel_rows(double *L_, char *lds_, const int n_, const int ld_, const int J_, const int jb_, const int fuse_ = 0) {
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_), J = QP_UNIFORM(J_), jb = QP_UNIFORM(jb_); /* wave-uniform arguments back to SGPRs */
   qp_gdouble *L = (qp_gdouble *)L_;
   FactorLds QP_LDS_AS &F = *QP_LDS_ARG(FactorLds, lds_);
@@ -582,9 +571,6 @@ QP_NI_FROWS void factor_panel_rows(double *L_, char *lds_, const int n_, const i
  * p(c2, c) are wave-uniform values fetched with v_readlane (no LDS round trip on the chain), one division per column,
  * then p(r, c2) <- fma(-l(r, c), p(c2, c), p(r, c2)) for c2 > c: the same fma per entry, in the same order (c
  * ascending), as the LDS form it replaces (measured there: ~1 us per column; the mpc-160 factorisation spent 40 % here). */
-#ifndef QP_NI_FDIAG
-#define QP_NI_FDIAG QPNI
-#endif
 QPD void factor_diag_block_body(char *lds_, const int fuse = 0, const int J = 0, const int jb = 0) {
   FactorLds QP_LDS_AS &F = *QP_LDS_ARG(FactorLds, lds_);
   constexpr int NB = QP_FNB;
@@ -622,14 +608,11 @@ QPD void factor_diag_block_body(char *lds_, const int fuse = 0, const int J = 0,
   }
 }
 
-QP_NI_FDIAG void factor_diag_block(char *lds_) { factor_diag_block_body(lds_); } /* as a real call (co_factor_diag) */
+QPNI void factor_diag_block(char *lds_) { factor_diag_block_body(lds_); } /* as a real call (co_factor_diag) */
 
-#ifndef QP_NI_FACTOR
-#define QP_NI_FACTOR QPNI
-#endif
 /* The three steps are inline (factor_panel_update_body, factor_diag_block_body, factor_panel_rows): one register frame per factorisation instead
  * of one per step and call (~140 calls, ~5300 dwords per lane through scratch at n = 1000; profiles/factor_scratch). */
-QP_NI_FACTOR void dense_factor(double *La_, double *Dga_, int n_, int ld_, char *ldsa_, int64_t *tdbga_, const double *fb_ = nullptr, double *fs_ = nullptr) {
+QPNI void dense_factor(double *La_, double *Dga_, int n_, int ld_, char *ldsa_, int64_t *tdbga_, const double *fb_ = nullptr, double *fs_ = nullptr) {
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_); /* wave-uniform arguments back to SGPRs ... */
   /* ... the pointers too: as VGPR pairs they stayed live -- spilled and reloaded -- through every loop of every step */
   double *L_ = QP_UNIFORM_PTR(La_), *Dg_ = QP_UNIFORM_PTR(Dga_);
@@ -721,12 +704,9 @@ struct SolveLds {
   double part[QP_SNB];
 };
 
-#ifndef QP_NI_SOLVE
-#define QP_NI_SOLVE QPNI
-#endif
 /* fwd_only != 0: only L y = b on the leading n x n block (n may be smaller than the panel), y returned unscaled:
  * the first step of a KKT row addition (L11 z = k12, Davis & Hager 2005) */
-QP_NI_SOLVE void dense_solve(const double *L_, const double *Dg_, int n_, int ld_, double *xg_, char *lds_, int lds_bytes, int64_t *tdbg_ = nullptr, int fwd_only_ = 0) {
+QPNI void dense_solve(const double *L_, const double *Dg_, int n_, int ld_, double *xg_, char *lds_, int lds_bytes, int64_t *tdbg_ = nullptr, int fwd_only_ = 0) {
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_), fwd_only = QP_UNIFORM(fwd_only_); /* wave-uniform arguments back to SGPRs */
   int64_t QP_LDS_AS *tdbg = (int64_t QP_LDS_AS *)tdbg_; /* null or the timers in the kernel's static LDS */
   const qp_gdouble *L = (const qp_gdouble *)L_, *Dg = (const qp_gdouble *)Dg_;
@@ -789,7 +769,7 @@ QP_NI_SOLVE void dense_solve(const double *L_, const double *Dg_, int n_, int ld
       for (int ch = 0; ch < NB; ch += QP_SOLVE_FCH) {
         double lv[QP_SOLVE_FCH];
 #pragma unroll
-        for (int cc = 0; cc < QP_SOLVE_FCH; cc++) lv[cc] = QP_LDNT(3, &L[(size_t)(J + ((ch + cc < jb) ? ch + cc : jb - 1)) * ld + i]);
+        for (int cc = 0; cc < QP_SOLVE_FCH; cc++) lv[cc] = QP_LDNT(&L[(size_t)(J + ((ch + cc < jb) ? ch + cc : jb - 1)) * ld + i]);
 #pragma unroll
         for (int cc = 0; cc < QP_SOLVE_FCH; cc++) if (ch + cc < jb) acc = QP_FMA(-lv[cc], xs[J + ch + cc], acc);
       }
@@ -835,7 +815,7 @@ QP_NI_SOLVE void dense_solve(const double *L_, const double *Dg_, int n_, int ld
           const qp_gdouble *col = L + (size_t)(J + ((c < jb) ? c : jb - 1)) * ld;
           double lv[BU];
 #pragma unroll
-          for (int u = 0; u < BU; u++) { const int i = i0 + 64 * u + lane; lv[u] = QP_LDNT(3, &col[(i < n) ? i : n - 1]); }
+          for (int u = 0; u < BU; u++) { const int i = i0 + 64 * u + lane; lv[u] = QP_LDNT(&col[(i < n) ? i : n - 1]); }
 #pragma unroll
           for (int u = 0; u < BU; u++) sacc[q] = QP_FMA(lv[u], xv[u], sacc[q]);
         }
@@ -1012,7 +992,7 @@ QPN void co_solve_forward(const double *L_, int n, int ld, double *x_, double *x
     for (int c0 = 0; c0 < NB; c0 += 16) { /* 16 column loads in flight per row */
       double lv[16];
 #pragma unroll
-      for (int c = 0; c < 16; c++) lv[c] = QP_LDNT(3, &L[(size_t)(J + ((c0 + c < jb) ? c0 + c : jb - 1)) * ld + i]);
+      for (int c = 0; c < 16; c++) lv[c] = QP_LDNT(&L[(size_t)(J + ((c0 + c < jb) ? c0 + c : jb - 1)) * ld + i]);
 #pragma unroll
       for (int c = 0; c < 16; c++) if (c0 + c < jb) acc = QP_FMA(-lv[c], T.part[c0 + c], acc);
     }
@@ -1057,7 +1037,7 @@ QPN void co_solve_backward(const double *L_, int n, int ld, double *x_, double *
       const int r0 = J + 4 * gl;
       double lv[4];
 #pragma unroll
-      for (int k = 0; k < 4; k++) lv[k] = (r0 + k < n) ? QP_LDNT(3, &L[(size_t)c * ld + r0 + k]) : 0.0;
+      for (int k = 0; k < 4; k++) lv[k] = (r0 + k < n) ? QP_LDNT(&L[(size_t)c * ld + r0 + k]) : 0.0;
       s = QP_FMA(lv[1], xb[1], lv[0] * xb[0]);
       s = QP_FMA(lv[2], xb[2], s);
       s = QP_FMA(lv[3], xb[3], s);
@@ -1185,19 +1165,10 @@ template <int KG> QPD int qp_rank_pivots(const double p, const int ln, const dou
   return (mode != QP_PIV_SEQ) ? 1 : 0;
 }
 
-
-/* lane R of every row of 16 lanes to all lanes of that row (DPP row_newbcast:R): no LDS, no SGPR */
-#ifdef QPALM_EMU
-template <int R> QPD double qp_row_bcast(double v) { const int lane = threadIdx.x & 63; return emu_exchange(v, (lane & ~15) | R); }
-#else
-template <int R> QPD double qp_row_bcast(double v) { /* ONE v_mov_b64_dpp: row_newbcast is the DPP control gfx90a+ allows on 64-bit moves */
-  return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + R, 0xf, 0xf, true);
-}
-#endif
 /* ranks r = R0 .. R1-1 of one rank group applied to a row: w_{OFF+r} += c0_r l, l += c1_r w_{OFF+r}, the pair (c0_r, c1_r) living in
- * lane r of every 16-lane row */
+ * lane r of every 16-lane row and reaching the row's lanes by DPP row broadcast (row_newbcast: no LDS, no SGPR) */
 #ifdef QPALM_EMU
-template <int K, int OFF, int R0, int R1, bool FIRST = true>
+template <int K, int OFF, int R0, int R1>
 QPD void qp_apply_ranks_dpp(const double cw0, const double cw1, double (&wrow)[K], double &l) { /* same values, one fiber round instead of 2 (R1 - R0) */
   const int lane = threadIdx.x & 63;
   emu_publish2(cw0, cw1);
@@ -1209,11 +1180,9 @@ QPD void qp_apply_ranks_dpp(const double cw0, const double cw1, double (&wrow)[K
   emu_wave_sync();
 }
 #else
-#ifndef QP_FMAC_DPP
-#define QP_FMAC_DPP 1 /* the broadcast folded into the FMA: v_fmac_f64_dpp (VOP2 + DPP row_newbcast, gfx90a+) -- two instructions per rank instead of
-                         four.  The compiler does not form it from v_mov_b64_dpp + v_fmac_f64 by itself (ROCm 7.2), hence the inline assembly. */
-#endif
-/* Eight ranks in ONE assembly statement: w_i <- fma(pair_x of lane R0 + i, l, w_i); l <- fma(pair_y of lane R0 + i, w_i, l), i = 0..7.
+/* The broadcast is folded into the FMA: v_fmac_f64_dpp (VOP2 + DPP row_newbcast, gfx90a+) -- two instructions per rank instead of four.
+ * The compiler does not form it from v_mov_b64_dpp + v_fmac_f64 by itself (ROCm 7.2), hence the inline assembly.
+ * Eight ranks in ONE assembly statement: w_i <- fma(pair_x of lane R0 + i, l, w_i); l <- fma(pair_y of lane R0 + i, w_i, l), i = 0..7.
  * (One statement per instruction would cost an s_nop between any two of them: the compiler's hazard recogniser assumes the worst
  * of inline assembly on gfx950 -- dst_sel / cvt-scale forwarding -- and that takes back half of what the fused form saves.)
  * A DPP operand must not have been written by one of the two preceding VALU instructions, and the compiler's hazard recogniser does
@@ -1228,45 +1197,36 @@ template <int R0> QPD void qp_fmac_bcast8(double *w, double &l, const double cw0
       : "+&v"(w[0]), "+&v"(w[1]), "+&v"(w[2]), "+&v"(w[3]), "+&v"(w[4]), "+&v"(w[5]), "+&v"(w[6]), "+&v"(w[7]), "+&v"(l)
       : "v"(cw0), "v"(cw1), "n"(R0), "n"(R0 + 1), "n"(R0 + 2), "n"(R0 + 3), "n"(R0 + 4), "n"(R0 + 5), "n"(R0 + 6), "n"(R0 + 7));
 }
-template <int K, int OFF, int R0, int R1, bool FIRST = true>
+template <int K, int OFF, int R0, int R1>
 QPD void qp_apply_ranks_dpp(const double cw0, const double cw1, double (&wrow)[K], double &l) {
-  if constexpr (QP_FMAC_DPP && R1 - R0 == 8 && OFF + R1 <= K) {
-    qp_fmac_bcast8<R0>(&wrow[OFF + R0], l, cw0, cw1);
-  } else if constexpr (R0 < R1 && OFF + R0 < K) {
-    const double c0 = qp_row_bcast<R0>(cw0), c1 = qp_row_bcast<R0>(cw1);
-    wrow[OFF + R0] = QP_FMA(c0, l, wrow[OFF + R0]);
-    l = QP_FMA(c1, wrow[OFF + R0], l);
-    qp_apply_ranks_dpp<K, OFF, R0 + 1, R1, false>(cw0, cw1, wrow, l);
-  }
+  static_assert(R1 - R0 == 8 && K % 8 == 0, "eight ranks at a time");
+  /* (else: ranks the instance does not have.  The one such call is the K = 8 instance's <8, 0, 8, 16>, which its callers put behind `KG > 8 && kk > 8`) */
+  if constexpr (OFF + R1 <= K) qp_fmac_bcast8<R0>(&wrow[OFF + R0], l, cw0, cw1);
 }
-#endif
-/* QP_RECUR_DPP = 1: the diagonal-block recurrence of the update sweep hands the (-w, -gamma) pair of rank r to the row lanes by DPP
- * row broadcast (the rank scalars are computed in every 16-lane row, lane & 15 = rank) instead of through the LDS table: one LDS
- * round trip per column instead of two.  The table is still written for the wavefronts that own the rows below the block. */
-#ifndef QP_RECUR_DPP
-#define QP_RECUR_DPP 1
 #endif
 #ifndef QP_AQD
 #define QP_AQD 4 /* columns in flight (entry of the staged square + its pairs) in the panel wave's "table s-1 on the rows of block s" loop */
 #endif
-#ifndef QP_OWN_A
-#define QP_OWN_A 1 /* staged square (QP_USQ): the entries L(rows of block s, columns of block s-1) are finished and written to HBM by the OWNERS of
-                      those rows, which apply table s-1 to them like to every other row below; the panel wave applies the same table to its LDS
-                      copy for the running w it needs (same FMAs in the same order: the same bits) and stores nothing.  Its one global store
-                      per column waited ~100 ns to be accepted by the CU's memory pipeline next to the owners' streams -- longer than the
-                      column's FMAs (tools/variants/README.md, "panel store probes": 312 -> 219 us per sweep with the store left out). */
-#endif
-#ifndef QP_SQ_WB
-#define QP_SQ_WB 0 /* 1 (measured in round 4: no gain, 5186-5191 against 5206-5216 QP/s same box): the panel wave writes the entries of the staged square back into LDS, not to HBM (see its loop) */
-#endif
-#ifndef QP_PANEL_A_DPP
-#define QP_PANEL_A_DPP (K <= 16) /* the same hand-over when the panel wave applies the finished table s-1 to the rows of block s (see there);
-                                    measured: K = 16 panel wave 57.0 -> 55.0 ms per QP; K = 32: slower (4.43 vs 4.65 k QP/s), so not there */
-#endif
-#ifndef QP_OWNER_DPP32
-#define QP_OWNER_DPP32 1 /* ... and in the owners' loop of the 32-rank form (one row per lane: a broadcast LDS read per rank and column serves two FMAs
-                            only, the LDS pipe of the CU is the bound; two lane-indexed reads per column + DPP broadcasts instead) */
-#endif
+
+/* The rows of an update sweep: rows r0 .. r0 + kk - 1 of the list "entering (cols), then leaving (cols_dn)" of sqrt(Sigma) A scattered into
+ * the running vectors Wst ([rank][n], cleared by the caller), one wavefront per row (lane, wid: in the caller's numbering of its wavefronts).
+ * Returns the first nonzero this thread met (n: none).  Shared by dense_updown, dense_updown_big and co_updown_init (IP, DP, WP: the
+ * pointers as the caller holds them -- global address space in the first two, generic in the coop form). */
+template <class IP, class DP, class WP>
+QPD int updown_scatter_rows(const IP Atp, const IP Ati, const DP Atss, const int n, const WP Wst, const IP cols,
+                            const int n_up, const IP cols_dn, const int r0, const int kk, const int lane, const int wid) {
+  int jmin = n;
+  for (int r = wid; r < kk; r += QP_NW) {
+    const int g = r0 + r;
+    const int t = (g < n_up) ? cols[g] : cols_dn[g - n_up];
+    for (int k = Atp[t] + lane; k < Atp[t + 1]; k += 64) {
+      const int i = Ati[k];
+      Wst[(size_t)r * n + i] = Atss[k];
+      jmin = (i < jmin) ? i : jmin;
+    }
+  }
+  return jmin;
+}
 
 /* ---------------------------------------------------------------------------------------------
  * K = 32 (round 4): TWICE the ranks per pass over the panel = half the panel traffic per rank.  Two things make that fit:
@@ -1279,16 +1239,13 @@ QPD void qp_apply_ranks_dpp(const double cw0, const double cw1, double (&wrow)[K
  *    rank within the group; the second group starts from the pivot the first one leaves).  Per entry this is the SAME sequence
  *    of operations as two 16-rank sweeps, so the factor is bit-identical to what the 16-rank form produces.
  * ------------------------------------------------------------------------------------------- */
-template <int RPT, int K>
-#ifndef QP_NI_UPDOWN
-#define QP_NI_UPDOWN QPNI
-#endif
 /* a real function (own register allocation, see qpalm_device.h): plain pointer arguments, re-typed inside.
  * Ranks [rk0, rk0 + rkn) of the list "entering rows, then leaving rows" are applied, K per sweep. */
-QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *Atss_, const int n_, const int ld_,
-                               double *L_, double *Dg_, double *Wst_, const int *cols_, int n_up_,
-                               const int *cols_dn_, int n_dn_, QpShared *S_, char *lds, int64_t *tdbg_, int pre_jmin_ = -1,
-                               double *fs_ = nullptr, int rk0_ = 0, int rkn_ = 0x7fffffff) {
+template <int RPT, int K>
+QPNI void dense_updown(const int *Atp_, const int *Ati_, const double *Atss_, const int n_, const int ld_,
+                       double *L_, double *Dg_, double *Wst_, const int *cols_, int n_up_,
+                       const int *cols_dn_, int n_dn_, QpShared *S_, char *lds, int64_t *tdbg_, int pre_jmin_ = -1,
+                       double *fs_ = nullptr, int rk0_ = 0, int rkn_ = 0x7fffffff) {
   /* arguments of a real function arrive in VGPRs; these are wave-uniform: back to SGPRs, so that the
    * loops they bound are scalar loops (not exec-mask loops) and v_readlane indices are scalars */
   const int n = QP_UNIFORM(n_), ld = QP_UNIFORM(ld_), n_up = QP_UNIFORM(n_up_), n_dn = QP_UNIFORM(n_dn_);
@@ -1333,23 +1290,15 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
     if (pre_jmin < 0) {
       for (int e = tid; e < kk * n; e += QP_T) Wst[e] = 0.0;
       __syncthreads();
-      for (int r = wid; r < kk; r += QP_NW) {
-        const int g = r0 + r;
-        const int t = (g < n_up) ? cols[g] : cols_dn[g - n_up];
-        for (int k = Atp[t] + lane; k < Atp[t + 1]; k += 64) {
-          const int i = Ati[k];
-          Wst[(size_t)r * n + i] = Atss[k];
-          jmin = (i < jmin) ? i : jmin;
-        }
-      }
+      jmin = updown_scatter_rows(Atp, Ati, Atss, n, Wst, cols, n_up, cols_dn, r0, kk, lane, wid);
     } else jmin = (pre_jmin < n) ? pre_jmin : n - 1;
     if (fuse) jmin = 0;
     jmin = QP_UNIFORM(block_imin(S, jmin)); /* same value in every lane: keep the block loops scalar */
-    /* lane r of every 16-lane row of the panel wave carries 1/alpha_r of rank 16 g + r (QP_RECUR_DPP; else lane r, G = 1); it runs on
-     * through the passes.  (alpha_r itself, and with it the reciprocal of the pivot before the rank, is needed by nothing here: p and
-     * gamma take 1/alpha only, so the column pays for ONE reciprocal per rank group.) */
+    /* lane r of every 16-lane row of the panel wave carries 1/alpha_r of rank 16 g + r; it runs on through the passes.  (alpha_r itself, and
+     * with it the reciprocal of the pivot before the rank, is needed by nothing here: p and gamma take 1/alpha only, so the column pays for
+     * ONE reciprocal per rank group.) */
     double ialpha[G], sg[G];
-    const int rl = QP_RECUR_DPP ? (lane & 15) : lane;
+    const int rl = lane & 15;
 #pragma unroll
     for (int g = 0; g < G; g++) {
       ialpha[g] = 1.0;
@@ -1387,7 +1336,9 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
     auto apply_table = [&](const int tb, const int Jc, const bool ok) QP_ALWAYS_INLINE {
       constexpr int QD = (K > 16) ? 2 * QP_TQD : QP_TQD; /* one row per thread, 8-byte accesses: twice the columns in flight */
       static_assert(NB % QD == 0, "queue depth divides the block");
-      constexpr bool ODPP = QP_OWNER_DPP32 && (K > 16); /* pairs by lane-indexed reads + DPP broadcast instead of K broadcast reads per column */
+      /* 32-rank form: the pairs by lane-indexed reads + DPP broadcast instead of K broadcast reads per column (one row per lane: a broadcast
+       * LDS read per rank and column serves two FMAs only, the LDS pipe of the CU is the bound) */
+      constexpr bool ODPP = (K > 16);
       const qp_pair QP_LDS_AS *tabO = (const qp_pair QP_LDS_AS *)QP_LDS_VBASE(&QP_CWG(U, tb, 0)[lane & 15][0]);
       const int i0 = R0 + tid * RPT;
       qp_gdouble *rowp = ok ? (L + (size_t)Jc * ld + i0) : (dummy + tid * RPT);
@@ -1410,11 +1361,11 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
             for (int g = 0; g < G; g++) cf[g] = tabO[c1 * K + 16 * g];
 #pragma unroll
             for (int rr = 0; rr < RPT; rr++) {
-              qp_apply_ranks_dpp<K, 0, 0, 8, false>(cf[0].x, cf[0].y, w[rr], l[rr]);
-              if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16, false>(cf[0].x, cf[0].y, w[rr], l[rr]);
+              qp_apply_ranks_dpp<K, 0, 0, 8>(cf[0].x, cf[0].y, w[rr], l[rr]);
+              if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16>(cf[0].x, cf[0].y, w[rr], l[rr]);
               if constexpr (G > 1) {
-                if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8, false>(cf[G - 1].x, cf[G - 1].y, w[rr], l[rr]);
-                if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16, false>(cf[G - 1].x, cf[G - 1].y, w[rr], l[rr]);
+                if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(cf[G - 1].x, cf[G - 1].y, w[rr], l[rr]);
+                if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16>(cf[G - 1].x, cf[G - 1].y, w[rr], l[rr]);
               }
             }
           } else {
@@ -1535,7 +1486,13 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
       const int jbn = (R1 - Jn < NB) ? ((R1 - Jn > 0) ? (R1 - Jn) : 0) : NB; /* 0 when block s is the last one of the pass */
       const int cur = s & 1, prv = cur ^ 1;
       long long tpe = QP_CLOCK();
-      constexpr bool OWNA = QP_OWN_A && QP_USQ && !QP_SQ_WB;
+      /* staged square (QP_USQ): the entries L(rows of block s, columns of block s-1) are finished and written to HBM by the OWNERS of those rows,
+       * which apply table s-1 to them like to every other row below; the panel wave applies the same table to its LDS copy for the running w
+       * it needs (same FMAs in the same order: the same bits) and stores nothing.  Its one global store per column waited ~100 ns to be
+       * accepted by the CU's memory pipeline next to the owners' streaming loads and stores -- longer than the column's FMAs
+       * (tools/variants/README.md, "panel store probes": 312 -> 219 us per sweep with the store left out; round 3's knock-outs: the owners'
+       * HBM traffic, not their FMAs or LDS reads, slowed that loop by a third). */
+      constexpr bool OWNA = QP_USQ;
       const int Ja = (OWNA && s > 0) ? J : Jn; /* first row the owners apply table s-1 to */
       const bool own_live0 = (R0 + 64 * RPT - 1 >= Ja); /* wavefront 0 still owns rows the owners work on */
       auto owner_block = [&]() QP_ALWAYS_INLINE {
@@ -1544,7 +1501,7 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
         bool any = false;
 #pragma unroll
         for (int rr = 0; rr < RPT; rr++) { const int i = R0 + tid * RPT + rr; any = any || (i >= Ja && i < R1); }
-        constexpr bool WAVES = MP && QP_OWNER_DPP32; /* DPP form: whole wavefronts take part (idle lanes work on their dummy cell) */
+        constexpr bool WAVES = MP; /* DPP form: whole wavefronts take part (idle lanes work on their dummy cell) */
         if (s > 0 && (WAVES ? (__ballot(any ? 1 : 0) != 0ull) : any)) {
           const int i0 = R0 + tid * RPT;
           apply_table(prv, Jp, i0 >= Ja && i0 < rlim);
@@ -1596,12 +1553,15 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
            * (Tried in round 2 and measured slower on MI355X in the full kernel, although faster in isolation: register
            * rotation of the (-w_j, -gamma) pairs, and two columns at a time skewed by one rank.  The panel wave is bound by
            * the number of instructions it issues, ~6.5 clk each, not by the FMA dependences.) */
-          /* QP_PANEL_A_DPP: the (-w_j, -gamma) pairs of a column are fetched with ONE lane-indexed 16-byte LDS read per rank group (lane
-           * & 15 = rank: every 16-lane row holds the group's pairs), QD columns ahead like the entries of L, and rank r's pair reaches
-           * the row lanes by DPP row broadcast as in the recurrence: K broadcast reads and their waits per column leave the chain. */
+          /* PADPP (the forms with at most 16 ranks; measured: K = 16 panel wave 57.0 -> 55.0 ms per QP, K = 32 slower, 4.43 against 4.65 k QP/s,
+           * so the 32-rank form keeps the broadcast reads): the (-w_j, -gamma) pairs of a column are fetched with ONE lane-indexed 16-byte LDS
+           * read per rank group (lane & 15 = rank: every 16-lane row holds the group's pairs), QD columns ahead like the entries of L, and rank
+           * r's pair reaches the row lanes by DPP row broadcast as in the recurrence: K broadcast reads and their waits per column leave the
+           * chain. */
           const qp_pair QP_LDS_AS *tabA = (const qp_pair QP_LDS_AS *)QP_LDS_VBASE(&QP_CWG(U, prv, 0)[lane & 15][0]);
-          qp_pair cfq[QP_PANEL_A_DPP ? QD : 1][G];
-          if (QP_PANEL_A_DPP) {
+          constexpr bool PADPP = (K <= 16);
+          qp_pair cfq[PADPP ? QD : 1][G];
+          if (PADPP) {
 #pragma unroll
             for (int cc = 0; cc < QD; cc++)
 #pragma unroll
@@ -1613,12 +1573,12 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
               const int c1 = c0 + u;
               double l = q[u];
               const int cpre = (c1 + QD < NB) ? c1 + QD : NB - 1;
-              if (QP_PANEL_A_DPP) {
-                qp_apply_ranks_dpp<K, 0, 0, 8, false>(cfq[u][0].x, cfq[u][0].y, wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
-                if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16, false>(cfq[u][0].x, cfq[u][0].y, wrow, l);
+              if (PADPP) {
+                qp_apply_ranks_dpp<K, 0, 0, 8>(cfq[u][0].x, cfq[u][0].y, wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
+                if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16>(cfq[u][0].x, cfq[u][0].y, wrow, l);
                 if constexpr (G > 1) {
-                  if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8, false>(cfq[u][G - 1].x, cfq[u][G - 1].y, wrow, l);
-                  if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16, false>(cfq[u][G - 1].x, cfq[u][G - 1].y, wrow, l);
+                  if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(cfq[u][G - 1].x, cfq[u][G - 1].y, wrow, l);
+                  if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16>(cfq[u][G - 1].x, cfq[u][G - 1].y, wrow, l);
                 }
               } else {
 #pragma unroll
@@ -1637,16 +1597,11 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
                 if (K > 16) QP_SCHED_BARRIER(); /* 32 ranks: one group of eight pairs in registers at a time */
               }
               }
-              /* QP_SQ_WB: the final entry goes back into the staged square (the owners write the square to HBM while they stage the next
-               * one), so that the serial chain issues no global-memory instruction at all: a global store of the panel wave queues up
-               * behind the owners' streaming loads and stores in the CU's memory pipeline (round 3's knock-outs: the owners' HBM traffic,
-               * not their FMAs or LDS reads, slowed this loop by a third). */
-              if (PSQ && QP_SQ_WB) { if (lane < NB) U.Lsq[cur][c1][lrow] = l; }
-              else if (!OWNA) rowp[(size_t)c1 * cstride] = l; /* (OWNA: the rows' owners write the entry) */
+              if (!OWNA) rowp[(size_t)c1 * cstride] = l; /* (OWNA: the rows' owners write the entry) */
               if (fuse) accp = QP_FMA(-l, U.ys[prv][c1], accp); /* column Jp + c1 is final for this row */
               QP_SCHED_BARRIER();
               q[u] = PSQ ? U.Lsq[cur][cpre][lrow] : rowp[(size_t)cpre * cstride]; /* refill AFTER the slot's register is free: no queue rotation on the back edge */
-              if (QP_PANEL_A_DPP) {
+              if (PADPP) {
 #pragma unroll
                 for (int g = 0; g < G; g++) cfq[u][g] = tabA[cpre * K + 16 * g];
               }
@@ -1684,8 +1639,8 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
             const int ln = QP_FRESH_LANE(lane);
             const double lcur = lnext;
             lnext = (ln > c1 + 1 && ln < jb) ? U.Ld[cur][ln][c1 + 1] : 0.0; /* in flight during this column (column NB is padding) */
-            /* QP_PANEL_TIMING == 2 (diagnostic build): ms_dbg[8..11] = the column's four links: pivot row through LDS to lane = rank /
-             * rank scalars / table entry through LDS back to every lane / the 2 K FMAs (each stamp drains the LDS queue first) */
+            /* QP_PANEL_TIMING == 2 (diagnostic build): ms_dbg[8], [9], [11] = the column's three links: pivot row through LDS to lane = rank /
+             * rank scalars / the 2 K FMAs with the pairs broadcast by DPP (the first stamps drain the LDS queue first) */
             long long tc0 = 0;
             if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); tc0 = QP_CLOCK(); }
             if (ln == c1) {
@@ -1695,7 +1650,7 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
             QP_WAVE_SYNC();
             /* rank-indexed scalars: lane = rank within its group (lanes >= kk carry w = 0 => gamma = 0: exact no-ops).  The groups of
              * 16 ranks follow each other in the same lanes; group g starts from the pivot group g-1 leaves. */
-            const int rk = QP_RECUR_DPP ? (ln & 15) : ln;
+            const int rk = ln & 15;
             double d0 = qp_readlane(dreg, c1);
             double nwv[G], ngam[G];
 #pragma unroll
@@ -1720,49 +1675,17 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
             }
             if (QP_PANEL_TIMING == 2) { double gg = ngam[0]; QP_OPAQUE_V(gg); const long long t = QP_CLOCK(); if (lane == 0) tdbg[9] += t - tc0; tc0 = t; }
             if (ln == c1) dreg = d0; /* final pivot of the column = value after the last rank */
-            if (!QP_RECUR_DPP) QP_WAVE_SYNC();
             /* rows of the block: lane = row.  Rows <= c1 are finished, their registers may be
              * overwritten freely, so no selects: w_r -= w_j l ; l -= gamma w_r  (2 FMAs per rank) */
             double l = lcur;
-            if (QP_RECUR_DPP) {
-              qp_apply_ranks_dpp<K, 0, 0, 8>(nwv[0], ngam[0], wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
-              if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16, false>(nwv[0], ngam[0], wrow, l);
-              if constexpr (G > 1) {
-                if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(nwv[1], ngam[1], wrow, l);
-                if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16, false>(nwv[1], ngam[1], wrow, l);
-              }
-            } else {
-              static_assert(QP_RECUR_DPP || G == 1, "the LDS form of the recurrence handles one rank group");
-              /* the first eight entries come back from LDS together; with more than eight ranks an entry's registers are refilled with
-               * the entry eight ranks further right after its two FMAs, so that the second group's LDS latency runs under the first
-               * group's FMA chain (it used to be requested only after that chain: a second exposed round trip per column) */
-              const qp_pair QP_LDS_AS *tab = (const qp_pair QP_LDS_AS *)&QP_CWG(U, cur, c1)[0][0];
-              qp_pair cf[8];
-#pragma unroll
-              for (int r = 0; r < 8; r++) cf[r] = tab[r];
-              if (QP_PANEL_TIMING == 2) { QP_DRAIN_LDS(); const long long t = QP_CLOCK(); if (lane == 0) tdbg[10] += t - tc0; tc0 = t; }
-              if (K > 8 && kk > 8) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                  wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
-                  l = QP_FMA(cf[r].y, wrow[r], l);
-                  cf[r] = tab[(8 + r < K) ? 8 + r : r];
-                  QP_SCHED_BARRIER();
-                }
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                  if (8 + r < K) {
-                    wrow[8 + r] = QP_FMA(cf[r].x, l, wrow[8 + r]);
-                    l = QP_FMA(cf[r].y, wrow[8 + r], l);
-                  }
-                }
-              } else {
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                  wrow[r] = QP_FMA(cf[r].x, l, wrow[r]);
-                  l = QP_FMA(cf[r].y, wrow[r], l);
-                }
-              }
+            /* the (-w, -gamma) pair of rank r reaches the row lanes by DPP row broadcast (the rank scalars are computed in every 16-lane row,
+             * lane & 15 = rank), not through the LDS table: one LDS round trip per column instead of two.  The table is still written for the
+             * wavefronts that own the rows below the block. */
+            qp_apply_ranks_dpp<K, 0, 0, 8>(nwv[0], ngam[0], wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
+            if (KG > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16>(nwv[0], ngam[0], wrow, l);
+            if constexpr (G > 1) {
+              if (kk > 16) qp_apply_ranks_dpp<K, 16, 0, 8>(nwv[1], ngam[1], wrow, l);
+              if (kk > 24) qp_apply_ranks_dpp<K, 16, 8, 16>(nwv[1], ngam[1], wrow, l);
             }
             const bool below = (ln > c1 && ln < jb); /* rows of the block below the column's diagonal entry */
             if (below) U.Ld[cur][ln][c1] = l;
@@ -1819,8 +1742,6 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
               if (s > 0) L[(size_t)(Jp + c1) * ld + (Jp + c)] = U.Ld[prv][c][c1];
               if (c < jbn) U.Ld[prv][c][c1] = L[(size_t)(Jn + c1) * ld + (Jn + c)];
             }
-            /* the square of the LAST phase (rows of block s-1, columns of block s-2: block s-1 is a full block) as the panel wave left it: back to HBM */
-            if (QP_SQ_WB && s >= 2) L[(size_t)(Jp - NB + c1) * ld + (Jp + c)] = U.Lsq[prv][c1][c];
             /* next phase: the panel wave applies table s to the rows of block s+1 */
             if (jbn > 0) U.Lsq[prv][c1][c] = (c < jbn) ? L[(size_t)(J + c1) * ld + (Jn + c)] : 0.0;
           }
@@ -1841,8 +1762,6 @@ QP_NI_UPDOWN void dense_updown(const int *Atp_, const int *Ati_, const double *A
       for (int e = tid; e < NB * NB; e += QP_T) {
         const int c1 = e / NB, c = e % NB;
         if (c > c1 && c < jbl) L[(size_t)(Jl + c1) * ld + (Jl + c)] = U.Ld[sl & 1][c][c1];
-        /* ... and the square the panel wave updated in the last phase (rows of the last block, columns of the one before) */
-        if (QP_SQ_WB && sl >= 1 && c < jbl) L[(size_t)(Jl - NB + c1) * ld + (Jl + c)] = U.Lsq[sl & 1][c1][c];
       }
     }
     if (MP && !last_pass) export_table((nblk - 1) & 1, Js + (nblk - 1) * NB, tid, QP_T); /* the pass's last table */
@@ -1870,17 +1789,15 @@ struct UpdownBigLds {
   double dd[QP_UNB];
 };
 /* the recurrence on one 32 x 32 diagonal block (in U.Ld / dreg, lane = row of the block) for kk <= K ranks: leaves the table
- * (-w_j, -gamma) of the block's columns in U.cwg, the new entries in U.Ld and the new pivots in dreg; lane r carries alpha_r */
-/* QP_PANEL_DPP = 1: the rank scalars are computed in every 16-lane row of the wavefront (lane & 15 = rank) and the (-w, -gamma)
+ * (-w_j, -gamma) of the block's columns in U.cwg, the new entries in U.Ld and the new pivots in dreg; lane r of every 16-lane row carries
+ * 1 / alpha_r (alpha_r itself is needed by no formula, see dense_updown) */
+/* The rank scalars are computed in every 16-lane row of the wavefront (lane & 15 = rank) and the (-w, -gamma)
  * pair of rank r reaches the row lanes by DPP row broadcast instead of through the LDS table (which is still written, for the
  * rows below the block, but not waited for): one LDS round trip per column instead of two.  Measured in DESIGN section 7. */
-#ifndef QP_PANEL_DPP
-#define QP_PANEL_DPP 1
-#endif
 template <int K>
 QPD void updown_big_panel(UpdownBigLds<K> QP_LDS_AS &U, const int lane, const int jb, const int kk, const double sg,
-                          double (&wrow)[K], double &dreg, double &alpha, double &ialpha, const int pivmode = QP_PIV_TREE) {
-  static_assert(K == 16 || !QP_PANEL_DPP, "the DPP form needs one rank per lane of a 16-lane row");
+                          double (&wrow)[K], double &dreg, double &ialpha, const int pivmode = QP_PIV_TREE) {
+  static_assert(K == 16, "one rank per lane of a 16-lane row");
   double lnext = (lane > 0 && lane < jb) ? U.Ld[lane][0] : 0.0;
 #pragma unroll 1
   for (int c1 = 0; c1 < jb; c1++) {
@@ -1892,37 +1809,69 @@ QPD void updown_big_panel(UpdownBigLds<K> QP_LDS_AS &U, const int lane, const in
       for (int r = 0; r < K; r++) U.Wt[r] = wrow[r];
     }
     QP_WAVE_SYNC();
-    const int rk = QP_PANEL_DPP ? (ln & (K - 1)) : ln;
+    const int rk = ln & (K - 1);
     const double wv = (rk < kk) ? U.Wt[rk & (K - 1)] : 0.0;
     const double d0 = qp_readlane(dreg, c1);
     const double p = sg * wv * wv * ialpha;
     double dnew, dprev;
     qp_rank_pivots<K>(p, ln, d0, pivmode, dnew, dprev);
-    const double rdn = qp_rcp(dnew), rdp = qp_rcp(dprev);
+    const double rdn = qp_rcp(dnew);
     const double gam = -sg * wv * ialpha * rdn;
     if (ln < K) { U.cwg[c1][ln][0] = -wv; U.cwg[c1][ln][1] = -gam; }
-    /* (alpha is read by no formula here either; it stays because the coop sweeps hand it from block to block in their published tables
-     * (CO_UD_TAB, hst): taking it out changes that layout and three callers, which dense_updown's change does not need) */
-    alpha = (wv == 0.0) ? alpha : alpha * dnew * rdp; /* zero in this column: exactly unchanged (see dense_updown) */
-    ialpha = (wv == 0.0) ? ialpha : ialpha * dprev * rdn;
+    ialpha = (wv == 0.0) ? ialpha : ialpha * dprev * rdn; /* zero in this column: exactly unchanged (see dense_updown) */
     { const double dfin = qp_readlane(dnew, kk - 1); if (ln == c1) dreg = dfin; }
-    if (QP_PANEL_DPP) {
-      double l = lcur;
-      qp_apply_ranks_dpp<K, 0, 0, 8>(-wv, -gam, wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
-      if (K > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16>(-wv, -gam, wrow, l);
-      if (ln > c1 && ln < jb) U.Ld[ln][c1] = l;
-    } else {
-      QP_WAVE_SYNC();
-      double l = lcur;
-#pragma unroll
-      for (int r = 0; r < K; r++) {
-        if (r >= kk) break;
-        wrow[r] = QP_FMA(U.cwg[c1][r][0], l, wrow[r]);
-        l = QP_FMA(U.cwg[c1][r][1], wrow[r], l);
-      }
-      if (ln > c1 && ln < jb) U.Ld[ln][c1] = l;
-    }
+    double l = lcur;
+    qp_apply_ranks_dpp<K, 0, 0, 8>(-wv, -gam, wrow, l); /* (ranks >= kk carry zero pairs: exact no-ops) */
+    if (K > 8 && kk > 8) qp_apply_ranks_dpp<K, 0, 8, 16>(-wv, -gam, wrow, l);
+    if (ln > c1 && ln < jb) U.Ld[ln][c1] = l;
     QP_SCHED_BARRIER();
+  }
+}
+
+/* Steps that dense_updown_big and the coop forms (co_updown_block / co_updown_persist) share (the scatter of the sweep's rows,
+ * updown_scatter_rows, stands in front of dense_updown, which uses it too). */
+/* (LP, DP, WP: the pointers as the caller holds them -- dense_updown_big's carry the global address space, the coop forms' are generic, and
+ * co_updown_persist keeps the running values of its diagonal rows in LDS) */
+/* diagonal block J (jb columns) and its pivots, HBM -> LDS */
+template <int K, class LP, class DP>
+QPD void updown_big_load_diag(UpdownBigLds<K> QP_LDS_AS &U, const LP L, const DP Dg, const int ld, const int J, const int jb, const int tid) {
+  for (int e = tid; e < jb * jb; e += QP_T) {
+    const int c1 = e / jb, c = e % jb;
+    if (c > c1) U.Ld[c][c1] = L[(size_t)(J + c1) * ld + (J + c)];
+  }
+  if (tid < jb) U.dd[tid] = Dg[J + tid];
+}
+/* the sign of the lane's rank: the same for every block of a sweep (every 16-lane row of the panel wave carries the K ranks) */
+template <int K>
+QPD double updown_big_sign(const int lane, const int kk, const int r0, const int n_up) {
+  const int rl = lane & (K - 1);
+  return (rl < kk) ? ((r0 + rl < n_up) ? 1.0 : -1.0) : 0.0;
+}
+/* panel-wave prologue (lane = row of the block): the row's running values (rank r at w[r * ws + off]) and its pivot */
+template <int K, class WP>
+QPD void updown_big_prologue(UpdownBigLds<K> QP_LDS_AS &U, const int lane, const int jb, const int kk,
+                             const WP w, const size_t ws, const int off, double (&wrow)[K], double &dreg) {
+#pragma unroll
+  for (int r = 0; r < K; r++) wrow[r] = (lane < jb && r < kk) ? w[(size_t)r * ws + off] : 0.0;
+  dreg = (lane < jb) ? U.dd[lane] : 1.0;
+}
+/* the finished diagonal block and its pivots back from the panel wave (each lane re-reads what it wrote itself): to block J of a matrix with
+ * leading dimension ld and its diagonal (the coop stage: J = 0, ld = 32) */
+template <int K, class LP, class DP>
+QPD void updown_big_store_diag(UpdownBigLds<K> QP_LDS_AS &U, const double dreg, const int lane, const int jb, const LP L, const int ld, const DP Dg, const int J) {
+  if (lane < jb) Dg[J + lane] = dreg;
+#pragma unroll 1
+  for (int c = 0; c < jb; c++)
+    if (lane > c && lane < jb) L[(size_t)(J + c) * ld + (J + lane)] = U.Ld[lane][c];
+}
+/* a finished table applied to one entry l of column c (cwg = U.cwg[c]): w_r -= w_j l ; l -= gamma w_r, ranks ascending */
+template <int K>
+QPD void updown_apply_entry(const double QP_LDS_AS (&cwg)[K][2], const int kk, double (&w)[K], double &l) {
+#pragma unroll
+  for (int r = 0; r < K; r++) {
+    if (r >= kk) break;
+    w[r] = QP_FMA(cwg[r][0], l, w[r]);
+    l = QP_FMA(cwg[r][1], w[r], l);
   }
 }
 
@@ -1949,20 +1898,11 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
     if (pre_jmin < 0) {
       for (int e = tid; e < kk * n; e += QP_T) Wst[e] = 0.0;
       __syncthreads();
-      for (int r = wid; r < kk; r += QP_NW) {
-        const int g = r0 + r;
-        const int t = (g < n_up) ? cols[g] : cols_dn[g - n_up];
-        for (int k = Atp[t] + lane; k < Atp[t + 1]; k += 64) {
-          const int i = Ati[k];
-          Wst[(size_t)r * n + i] = Atss[k];
-          jmin = (i < jmin) ? i : jmin;
-        }
-      }
+      jmin = updown_scatter_rows(Atp, Ati, Atss, n, Wst, cols, n_up, cols_dn, r0, kk, lane, wid);
     } else jmin = (pre_jmin < n) ? pre_jmin : n - 1;
     jmin = QP_UNIFORM(block_imin(S, jmin));
-    double alpha = 1.0, ialpha = 1.0; /* lane r of wavefront 0 carries alpha_r and 1/alpha_r */
-    const int rl = QP_PANEL_DPP ? (lane & (K - 1)) : lane, grank = r0 + rl; /* QP_PANEL_DPP: every 16-lane row of the panel wave carries the K ranks */
-    const double sg = (rl < kk) ? ((grank < n_up) ? 1.0 : -1.0) : 0.0;
+    double ialpha = 1.0; /* lane r of every 16-lane row of wavefront 0 carries 1/alpha_r */
+    const double sg = updown_big_sign<K>(lane, kk, r0, n_up);
     const int J0 = (jmin / NB) * NB;
     if (tid == 0) {
       tdbg[QPG_CNT_SWEEPS] += 1;
@@ -1971,22 +1911,13 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
     for (int J = J0; J < n; J += NB) {
       const int jb = (n - J < NB) ? (n - J) : NB;
       __syncthreads();
-      for (int e = tid; e < jb * jb; e += QP_T) { /* diagonal block to LDS */
-        const int c1 = e / jb, c = e % jb;
-        if (c > c1) U.Ld[c][c1] = L[(size_t)(J + c1) * ld + (J + c)];
-      }
-      if (tid < jb) U.dd[tid] = Dg[J + tid];
+      updown_big_load_diag<K>(U, L, Dg, ld, J, jb, tid);
       __syncthreads();
       if (wid == 0) { /* panel wave: lane = row of the block, the recurrence of dense_updown */
-        double wrow[K];
-#pragma unroll
-        for (int r = 0; r < K; r++) wrow[r] = (lane < jb && r < kk) ? Wst[(size_t)r * n + J + lane] : 0.0;
-        double dreg = (lane < jb) ? U.dd[lane] : 1.0;
-        updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, alpha, ialpha, QP_UNIFORM(S.seq_ranks));
-        if (lane < jb) Dg[J + lane] = dreg;
-#pragma unroll 1
-        for (int c = 0; c < jb; c++)
-          if (lane > c && lane < jb) L[(size_t)(J + c) * ld + (J + lane)] = U.Ld[lane][c];
+        double wrow[K], dreg;
+        updown_big_prologue<K>(U, lane, jb, kk, Wst, (size_t)n, J + lane, wrow, dreg);
+        updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, ialpha, QP_UNIFORM(S.seq_ranks));
+        updown_big_store_diag<K>(U, dreg, lane, jb, L, ld, Dg, J);
       }
       __syncthreads();
       /* rows below the block: one row per thread and chunk, its K running values from / to HBM */
@@ -1997,12 +1928,7 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
 #pragma unroll 1
         for (int c1 = 0; c1 < jb; c1++) {
           double l = L[(size_t)(J + c1) * ld + i];
-#pragma unroll
-          for (int r = 0; r < K; r++) {
-            if (r >= kk) break;
-            w[r] = QP_FMA(U.cwg[c1][r][0], l, w[r]);
-            l = QP_FMA(U.cwg[c1][r][1], w[r], l);
-          }
+          updown_apply_entry<K>(U.cwg[c1], kk, w, l);
           L[(size_t)(J + c1) * ld + i] = l;
         }
 #pragma unroll
@@ -2020,9 +1946,9 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
  * with ONE LAUNCH PER BLOCK COLUMN.  Every workgroup repeats the recurrence on the 32 x 32 diagonal block (a few microseconds)
  * from the same inputs and then applies the table to its share of the rows below; the kernel boundary orders block J + 1
  * after block J.  Workgroup 0 owns the block's outputs: the new diagonal block and pivots go to a stage (the other workgroups
- * may still be reading the old ones) and are written into L / D by the NEXT launch; the running alpha_r alternate between two
+ * may still be reading the old ones) and are written into L / D by the NEXT launch; the running 1 / alpha_r alternate between two
  * buffers.  State of one update, in the slot's stash area of Wst (hst = Wst + K n + QPG_DUMMY):
- *   hst[0..4K)  alpha, 1/alpha: buffer (J / 32) & 1 is read, the other written      hst[CO_UD_JMIN] first nonzero row
+ *   hst[0..2K)  1/alpha: buffer (J / 32) & 1 is read, the other written             hst[CO_UD_JMIN] first nonzero row
  *   hst[CO_UD_STAGED] block column held by the stage (-1 none)    hst[CO_UD_D ..) 32 pivots    hst[CO_UD_L ..) 32 x 32 entries
  * The arithmetic per entry is dense_updown_big's, so the factor is bit-identical to the one-workgroup sweep's.
  * ------------------------------------------------------------------------------------------- */
@@ -2036,23 +1962,15 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
 template <int K>
 QPD void co_updown_init(const int *Atp, const int *Ati, const double *Atss, const int n, double *Wst, double *hst, const int *cols, const int n_up,
                         const int *cols_dn, const int r0, const int kk, const int phase, QpShared &S, const int wg, const int nwg) {
+  static_assert(2 * K <= CO_UD_JMIN, "the two buffers of 1 / alpha end in front of the sweep's scalars");
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (phase == 0) {
     for (size_t e = (size_t)wg * QP_T + tid; e < (size_t)kk * n; e += (size_t)nwg * QP_T) Wst[e] = 0.0;
     return;
   }
-  int jmin = n;
-  for (int r = wid; r < kk; r += QP_NW) {
-    const int g = r0 + r;
-    const int t = (g < n_up) ? cols[g] : cols_dn[g - n_up];
-    for (int k = Atp[t] + lane; k < Atp[t + 1]; k += 64) {
-      const int i = Ati[k];
-      Wst[(size_t)r * n + i] = Atss[k];
-      jmin = (i < jmin) ? i : jmin;
-    }
-  }
+  int jmin = updown_scatter_rows(Atp, Ati, Atss, n, Wst, cols, n_up, cols_dn, r0, kk, lane, wid);
   jmin = block_imin(S, jmin);
-  if (tid < 4 * K) hst[tid] = 1.0;
+  if (tid < 2 * K) hst[tid] = 1.0;
   if (tid == 0) { hst[CO_UD_JMIN] = (double)((jmin < n) ? jmin : n - 1); hst[CO_UD_STAGED] = -1.0; }
 }
 /* block column J (J >= n: only the pending stage is written back) */
@@ -2078,28 +1996,17 @@ QPD void co_updown_block(const int n, const int ld, double *L, double *Dg, doubl
   }
   if (J >= n) return;
   const int jb = (n - J < NB) ? (n - J) : NB, par = (J / NB) & 1;
-  for (int e = tid; e < jb * jb; e += QP_T) { /* diagonal block to LDS */
-    const int c1 = e / jb, c = e % jb;
-    if (c > c1) U.Ld[c][c1] = L[(size_t)(J + c1) * ld + (J + c)];
-  }
-  if (tid < jb) U.dd[tid] = Dg[J + tid];
+  updown_big_load_diag<K>(U, L, Dg, ld, J, jb, tid);
   __syncthreads();
   if (wid == 0) {
-    double wrow[K];
-#pragma unroll
-    for (int r = 0; r < K; r++) wrow[r] = (lane < jb && r < kk) ? Wst[(size_t)r * n + J + lane] : 0.0;
-    double dreg = (lane < jb) ? U.dd[lane] : 1.0;
-    const int rl = QP_PANEL_DPP ? (lane & (K - 1)) : lane;
-    double alpha = (rl < K) ? hst[par * 2 * K + rl] : 1.0, ialpha = (rl < K) ? hst[par * 2 * K + K + rl] : 1.0;
-    const int grank = r0 + rl;
-    const double sg = (rl < kk) ? ((grank < n_up) ? 1.0 : -1.0) : 0.0;
-    updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, alpha, ialpha, pivmode);
+    double wrow[K], dreg;
+    updown_big_prologue<K>(U, lane, jb, kk, Wst, (size_t)n, J + lane, wrow, dreg);
+    const double sg = updown_big_sign<K>(lane, kk, r0, n_up);
+    double ialpha = hst[par * K + (lane & (K - 1))];
+    updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, ialpha, pivmode);
     if (wg == 0) {
-      if (lane < K) { hst[(1 - par) * 2 * K + lane] = alpha; hst[(1 - par) * 2 * K + K + lane] = ialpha; }
-      if (lane < jb) hst[CO_UD_D + lane] = dreg;
-#pragma unroll 1
-      for (int c = 0; c < jb; c++)
-        if (lane > c && lane < jb) hst[CO_UD_L + c * NB + lane] = U.Ld[lane][c];
+      if (lane < K) hst[(1 - par) * K + lane] = ialpha;
+      updown_big_store_diag<K>(U, dreg, lane, jb, hst + CO_UD_L, NB, hst + CO_UD_D, 0);
       if (lane == 0) hst[CO_UD_STAGED] = (double)J;
     }
   }
@@ -2120,14 +2027,7 @@ QPD void co_updown_block(const int n, const int ld, double *L, double *Dg, doubl
   __syncthreads();
   if (rower && i0 < n) {
 #pragma unroll
-    for (int c = 0; c < NB; c++) {
-#pragma unroll
-      for (int r = 0; r < K; r++) {
-        if (r >= kk) break;
-        w[r] = QP_FMA(U.cwg[c][r][0], l[c], w[r]);
-        l[c] = QP_FMA(U.cwg[c][r][1], w[r], l[c]);
-      }
-    }
+    for (int c = 0; c < NB; c++) updown_apply_entry<K>(U.cwg[c], kk, w, l[c]);
 #pragma unroll
     for (int c = 0; c < NB; c++) L[(size_t)(J + c) * ld + i0] = l[c];
 #pragma unroll
@@ -2142,14 +2042,7 @@ QPD void co_updown_block(const int n, const int ld, double *L, double *Dg, doubl
 #pragma unroll
         for (int c = 0; c < 16; c++) l[c] = L[(size_t)(J + h + c) * ld + i];
 #pragma unroll
-        for (int c = 0; c < 16; c++) {
-#pragma unroll
-          for (int r = 0; r < K; r++) {
-            if (r >= kk) break;
-            w[r] = QP_FMA(U.cwg[h + c][r][0], l[c], w[r]);
-            l[c] = QP_FMA(U.cwg[h + c][r][1], w[r], l[c]);
-          }
-        }
+        for (int c = 0; c < 16; c++) updown_apply_entry<K>(U.cwg[h + c], kk, w, l[c]);
 #pragma unroll
         for (int c = 0; c < 16; c++) L[(size_t)(J + h + c) * ld + i] = l[c];
       }
@@ -2165,14 +2058,14 @@ QPD void co_updown_block(const int n, const int ld, double *L, double *Dg, doubl
  * two wavefronts, the row's kk running values in registers from the first block to the last instead of through HBM at every block --
  * and the four diagonal blocks inside those rows: it applies the tables of the blocks in front of its rows as their owners publish
  * them, then runs the recurrence of its own blocks (updown_big_panel, once per block in the whole grid), publishes each table
- * ((-w, -gamma) per column and rank + the running alpha: 8.4 KB) and a counter, and applies it to its remaining rows.  The only
+ * ((-w, -gamma) per column and rank + the running 1 / alpha: 8.3 KB) and a counter, and applies it to its remaining rows.  The only
  * data that crosses workgroups are the tables: L, D and the running vectors of a row are touched by its owner alone.
  * Hand-off: QP_RELEASE_AGENT / QP_ACQUIRE_AGENT above; one counter (flags[0] = blocks published so far, set to the first block
  * by the init launch), polled by one lane with a bounded spin (flags[1] != 0: gave up -- the host reports it, nothing hangs); the
  * grid is one workgroup per 128 rows (at most 64: all resident), workgroup g waits only for workgroups < g.
  * The arithmetic per entry is co_updown_block's: bit-identical factors.
  * ------------------------------------------------------------------------------------------- */
-#define CO_UD_TAB(K) (QP_UNB * (K) * 2 + 2 * (K)) /* doubles per published table: the block's (-w, -gamma) pairs, then alpha and 1 / alpha per rank */
+#define CO_UD_TAB(K) (QP_UNB * (K) * 2 + (K)) /* doubles per published table: the block's (-w, -gamma) pairs, then 1 / alpha per rank */
 template <int K>
 QPD void co_updown_persist(const int n, const int ld, double *L, double *Dg, const double *Wst, const double *hst, double *tab, int *flags,
                            const int r0, const int kk, const int n_up, char *lds, const int wg, QpShared &S, const int pivmode) {
@@ -2197,7 +2090,10 @@ QPD void co_updown_persist(const int n, const int ld, double *L, double *Dg, con
   double w[K], l[NB];
 #pragma unroll
   for (int r = 0; r < K; r++) w[r] = (live && r < kk) ? Wst[(size_t)r * n + i] : 0.0;
-  auto apply_rows = [&](const int J) QP_ALWAYS_INLINE { /* table in U.cwg, the row's 32 entries of block column J in l */
+  /* table in U.cwg, the row's 32 entries of block column J in l.  updown_apply_entry's loop written out: only in this form does the compiler
+   * keep w and l in fixed registers here; through the helper it indexes w[] at run time (4288 s_set_gpr_idx_on / _off in k_co_sweep against
+   * none, 14.3 k instructions against 11.2 k: profiles/sweep_cleanup/README.md) */
+  auto apply_rows = [&](const int J) QP_ALWAYS_INLINE {
 #pragma unroll
     for (int c = 0; c < NB; c++) {
 #pragma unroll
@@ -2243,15 +2139,11 @@ QPD void co_updown_persist(const int n, const int ld, double *L, double *Dg, con
     next = upto;
   }
   /* ---- my own blocks ---- */
-  double alpha = 1.0, ialpha = 1.0;
-  bool have_alpha = false;
+  double ialpha = 1.0;
+  bool have_carry = false;
   for (int b = (bown0 > bstart) ? bown0 : bstart; b < bown1; b++) {
     const int J = b * NB, jb = (n - J < NB) ? (n - J) : NB;
-    for (int e = tid; e < jb * jb; e += QP_T) {
-      const int c1 = e / jb, c = e % jb;
-      if (c > c1) U.Ld[c][c1] = L[(size_t)(J + c1) * ld + (J + c)];
-    }
-    if (tid < jb) U.dd[tid] = Dg[J + tid];
+    updown_big_load_diag<K>(U, L, Dg, ld, J, jb, tid);
     if (live && i >= J && i < J + jb) {
 #pragma unroll
       for (int r = 0; r < K; r++) wd[(i - J) * K + r] = w[r];
@@ -2263,30 +2155,20 @@ QPD void co_updown_persist(const int n, const int ld, double *L, double *Dg, con
     }
     __syncthreads();
     if (wid == 0) {
-      double wrow[K];
-#pragma unroll
-      for (int r = 0; r < K; r++) wrow[r] = (lane < jb && r < kk) ? wd[lane * K + r] : 0.0;
-      double dreg = (lane < jb) ? U.dd[lane] : 1.0;
-      const int rl = QP_PANEL_DPP ? (lane & (K - 1)) : lane;
-      if (!have_alpha) { /* the carry of the block in front of mine arrived with its table */
-        if (b > bstart) {
-          const double *T = tab + (size_t)(b - 1) * CO_UD_TAB(K) + NB * K * 2;
-          alpha = (rl < K) ? T[rl] : 1.0; ialpha = (rl < K) ? T[K + rl] : 1.0;
-        }
-        have_alpha = true;
+      double wrow[K], dreg;
+      updown_big_prologue<K>(U, lane, jb, kk, wd, (size_t)1, lane * K, wrow, dreg); /* wd is [row][K]: rank stride 1, the lane's row at lane * K */
+      if (!have_carry) { /* the carry of the block in front of mine arrived with its table */
+        if (b > bstart) ialpha = (tab + (size_t)(b - 1) * CO_UD_TAB(K) + NB * K * 2)[lane & (K - 1)];
+        have_carry = true;
       }
-      const int grank = r0 + rl;
-      const double sg = (rl < kk) ? ((grank < n_up) ? 1.0 : -1.0) : 0.0;
-      updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, alpha, ialpha, pivmode);
+      const double sg = updown_big_sign<K>(lane, kk, r0, n_up);
+      updown_big_panel<K>(U, lane, jb, kk, sg, wrow, dreg, ialpha, pivmode);
       QP_WAVE_SYNC();
-      if (lane < jb) Dg[J + lane] = dreg;
-#pragma unroll 1
-      for (int c = 0; c < jb; c++)
-        if (lane > c && lane < jb) L[(size_t)(J + c) * ld + (J + lane)] = U.Ld[lane][c];
+      updown_big_store_diag<K>(U, dreg, lane, jb, L, ld, Dg, J);
       if (R1 < n) { /* somebody owns rows under mine: publish */
         double *T = tab + (size_t)b * CO_UD_TAB(K);
         for (int e = lane; e < NB * K * 2; e += 64) T[e] = cw[e];
-        if (lane < K) { T[NB * K * 2 + lane] = alpha; T[NB * K * 2 + K + lane] = ialpha; }
+        if (lane < K) T[NB * K * 2 + lane] = ialpha;
         QP_DRAIN_VMEM();
         if (lane == 0) {
           QP_RELEASE_AGENT();
