@@ -315,6 +315,33 @@ typedef struct {
   qpg_int         *passes;    /* out [B] */
 } QPGDeviceAdjoint;
 int  qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io);
+/* The tangent of the solved batch: how the stored solutions move when q, the bounds and the stored entries of Q and A move along ONE direction
+ * (DESIGN.md section 13).  Per member, with (x, y) its stored solution and J, K as for the adjoint above (the same rule for J and its sides, the
+ * same active_in; an equality row counts as lower, so only dbmin is read there):
+ *   r1 = -(dq + dQ x + dA' y)     (y: the stored y of EVERY row),      r2_i = db_i - (dA x)_i for i in J, db_i = dbmin_i on a lower-active row,
+ *   dbmax_i on an upper-active one;      K [dx; dy_J] = [r1; r2],  dy_i = 0 outside J.
+ * dQx / dAx are read in the layout qpg_batch_update_Q_A takes and the adjoint writes: entry k belongs to the k-th entry the caller passed to
+ * qpg_batch_set_problem*; a stored lower entry of Q stands for both symmetric positions, upper entries and the padding up to nnzQ_max / nnzA_max are
+ * ignored.  On inactive rows dbmin, dbmax and (dA x)_i are not read.  A NULL direction array is a zero one (the same bits as an array of zeros).
+ * K is symmetric, so this is the adjoint's solve on another right-hand side: the same fresh factor, refinement, stopping rule, pass cap (200), flag /
+ * resid / passes, and <gx, dx> + <gy, dy> = <adjoint outputs of (gx, gy), direction> up to the rounding of the two solves.  With flag 1 or 2 dx and
+ * dy of the member are zero.  Entries beyond a sized member's own n / m are ignored on input and zero on output.  Synchronous; all arrays in device
+ * memory; inputs are only read; one deterministic launch (no floating-point atomics: two calls on the same state return the same bits).  The call
+ * may overwrite what the adjoint may overwrite and leaves everything else: solve -> tangent -> step is bit for bit solve -> step.
+ * QPG_ERR_INVALID before qpg_batch_setup, while a solve is in progress, for an active_in entry outside {-1, 0, 1} and when all five direction
+ * arrays are NULL; QPG_ERR_UNSUPPORTED for FACTORIZE_KKT batches, coop mode and nonconvex settings. */
+typedef struct {
+  const qpg_float *dq;            /* [B][n] or NULL = zero */
+  const qpg_float *dbmin, *dbmax; /* [B][m] or NULL = zero */
+  const qpg_float *dQx, *dAx;     /* [B][nnzQ_max], [B][nnzA_max] or NULL = zero */
+  const qpg_int   *active_in;     /* [B][m] or NULL */
+  qpg_float       *dx, *dy;       /* out [B][n], [B][m]; either may be NULL */
+  qpg_int         *active_out;    /* out [B][m]: the set used */
+  qpg_int         *flag;          /* out [B] */
+  qpg_float       *resid;         /* out [B] */
+  qpg_int         *passes;        /* out [B] */
+} QPGDeviceTangent;
+int  qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -14,6 +14,11 @@
  * SpMVs for the residual, one more and a triangular solve for du, one more for dw.  It stops with the correction of the first residual that has
  * ||r||inf <= 4 eps (||K~||inf ||z||inf + ||rhs||inf) (a backward-stable solve), or at the pass cap (flag 1).
  *
+ * The tangent (qpg_batch_tangent_device) is the same solve, K being symmetric, on the right-hand side of a direction of the data:
+ *   r1 = -(dq + dQ x + dA' y),  r2_i = db_i - (dA x)_i on J,  K [dx; dy_J] = [r1; r2]  -- a mode of the same kernel (qpg_adjoint_args.tangent).
+ * sens_setup (step 1: active set, scaled solution, ||K~||inf, the fresh factor) and sens_refine (step 2: the refinement on a given right-hand side and
+ * the way back to the caller's scaling) are shared as one copy of the code; adj_rhs / tan_rhs and the outputs are what differs.
+ *
  * Scratch: vectors a finished solve leaves behind and the next one rebuilds before it reads them (d, temp_n, delta_x, dphi, z, temp_m, delta_y,
  * the line-search scratch, enter / leave) and the workgroup's factor slot.  The active flags form_schur / sp_factor read are saved and put back
  * (update_sigma of a later solve may read them before its first Newton step).  x, y, the stored solution, sigma, gamma, Qx / Ax products and
@@ -24,14 +29,230 @@
 
 QPD int adj_bad(double v) { return (qabs(v) <= 1.7976931348623157e308) ? 0 : 1; } /* NaN or infinite */
 
+/* The vectors of a member the sensitivity solve works on (see "Scratch" above) */
+struct SensVecs {
+  double *u, *w, *xs, *rhs1, *r1, *rhs2, *r2, *t;
+  int *sgn, *keep, *act;
+};
+QPD SensVecs sens_vecs(const QpArrays &a) {
+  SensVecs v;
+  v.u = a.delta_x(); v.w = a.temp_m(); v.xs = a.d(); v.rhs1 = a.dphi(); v.r1 = a.temp_n(); v.rhs2 = a.z(); v.r2 = a.delta_y(); v.t = a.ls_delta();
+  v.sgn = a.enter(); v.keep = a.leave(); v.act = a.active();
+  return v;
+}
+
+/* ---- step 1 of a sensitivity solve (adjoint and tangent): the scaled solution xs, the active set (sgn; the flags form_schur / sp_factor read are saved
+ * in keep), z = [u; w] = 0, and F = Q~ (+ I / gamma) + A~_J' Sigma_J A~_J factorised afresh: the slot may hold another member's factor, or this member's
+ * for another set.  Returns ||K~||inf (largest absolute row sum). ---- */
 template <int RPT>
-QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int slot, IterShared &I, char *lds) {
+QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, const int64_t *active_in, int b, int slot, IterShared &I, char *lds) {
   constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
   const qpg_settings &st = *V.settings;
+  const int n = a.n, m = a.m, tid = threadIdx.x;
+  const size_t om = (size_t)b * V.m;
+  double *L = V.L + (size_t)slot * V.ld * V.nfac, *Dg = V.Dg + (size_t)slot * V.nfac;
+  const int scal = I.s.has_scaling, prox = qp_prox(st, I.s);
+  const double c = I.s.sc_c, gam = I.s.gamma;
+  for (int j = tid; j < n; j += QP_T) {
+    v.xs[j] = scal ? a.sol_x()[j] * a.Dinv()[j] : a.sol_x()[j];
+    v.u[j] = 0.0;
+  }
+  __syncthreads();
+  spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)v.xs, [&](int r, double s) { v.t[r] = s; });
+  __syncthreads();
+  for (int i = tid; i < m; i += QP_T) {
+    int sg;
+    if (active_in) { const int64_t av = active_in[om + i]; sg = (av < 0) ? -1 : ((av > 0) ? 1 : 0); }
+    else { /* set_active_constraints (newton.c:122-131) on the stored solution; an equality row counts as lower */
+      double yv = a.sol_y()[i];
+      if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
+      const double axys = v.t[i] + 1 * (yv * a.sigma_inv()[i]);
+      const double lo = a.bmin()[i], hi = a.bmax()[i];
+      sg = (lo == hi || axys <= lo) ? -1 : ((axys >= hi) ? 1 : 0);
+    }
+    v.sgn[i] = sg; v.keep[i] = v.act[i]; v.act[i] = (sg != 0) ? 1 : 0;
+    v.w[i] = 0.0;
+  }
+  __syncthreads();
+  double vm[1] = {0.0}, vs[1] = {0.0};
+  for (int j = tid; j < n; j += QP_T) {
+    double s = 0.0;
+    for (int k = a.Qfp()[j]; k < a.Qfp()[j + 1]; k++) s += qabs(a.Qfx()[k]);
+    for (int k = a.Ap()[j]; k < a.Ap()[j + 1]; k++) if (v.sgn[a.Ai()[k]]) s += qabs(a.Ax()[k]);
+    vm[0] = qmax(vm[0], s);
+  }
+  for (int i = tid; i < m; i += QP_T) {
+    if (!v.sgn[i]) continue;
+    double s = 0.0;
+    for (int k = a.Atp()[i]; k < a.Atp()[i + 1]; k++) s += qabs(a.Atx()[k]);
+    vm[0] = qmax(vm[0], s);
+  }
+  block_reduce<1, 0>(I.S, vm, vs);
+  if constexpr (SPARSE) {
+    const SpArrays SP = sp_arrays(V, b, slot, Dg, lds);
+    if (QP_CALL_BLOCK()) sp_factor(V, b, n, SP, true, prox != 0, gam);
+  } else {
+    form_schur(V, b, n, L, false, true, prox != 0, gam, I.S, lds);
+    dev_factor<RPT>(V, n, L, Dg, lds, I.s.ticks_dbg);
+  }
+  return vm[0];
+}
+
+/* ---- step 2: refinement on K~ z = [rhs1; rhs2], z = [u; w] (zero on entry), on the factor sens_setup left; then z back in the caller's scaling
+ * (u = D u~, w = E w~ / c; zeros when flagged) and the flags of the active set back where the next solve expects them ---- */
+template <int RPT>
+QPN void sens_refine(const qpg_view &V, const QpArrays &a, const SensVecs &v, int b, int slot, IterShared &I, char *lds, double normK, int max_pass,
+                     int &flag, int &passes, double &ratio) {
+  constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
+  const int n = a.n, m = a.m, tid = threadIdx.x;
+  const int scal = I.s.has_scaling;
+  double *L = V.L + (size_t)slot * V.ld * V.nfac, *Dg = V.Dg + (size_t)slot * V.nfac;
+  double *u = v.u, *w = v.w, *xs = v.xs, *rhs1 = v.rhs1, *r1 = v.r1, *rhs2 = v.rhs2, *r2 = v.r2, *t = v.t;
+  const int *sgn = v.sgn;
+  double vm[2] = {0.0, 0.0}, vs[1] = {0.0};
+  for (int j = tid; j < n; j += QP_T) vm[0] = qmax(vm[0], qabs(rhs1[j]));
+  for (int i = tid; i < m; i += QP_T) if (sgn[i]) vm[0] = qmax(vm[0], qabs(rhs2[i]));
+  block_reduce<1, 0>(I.S, vm, vs);
+  const double rhsn = vm[0];
+  for (int pass = 0;; pass++) {
+    __syncthreads();
+    spmv_rows<8>(n, a.Qfp(), a.Qfi(), a.Qfx(), (const double *)u, [&](int r, double s) { r1[r] = rhs1[r] - s; });
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)u, [&](int r, double s) { r2[r] = sgn[r] ? rhs2[r] - s : 0.0; });
+    __syncthreads();
+    spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)w, [&](int r, double s) { r1[r] = r1[r] - s; });
+    __syncthreads();
+    vm[0] = 0.0; vm[1] = 0.0; vs[0] = 0.0;
+    for (int j = tid; j < n; j += QP_T) {
+      vm[0] = qmax(vm[0], qabs(r1[j])); vm[1] = qmax(vm[1], qabs(u[j]));
+      vs[0] += (double)(adj_bad(r1[j]) | adj_bad(u[j]));
+    }
+    for (int i = tid; i < m; i += QP_T) {
+      vm[0] = qmax(vm[0], qabs(r2[i])); vm[1] = qmax(vm[1], qabs(w[i]));
+      vs[0] += (double)(adj_bad(r2[i]) | adj_bad(w[i]));
+    }
+    block_reduce<2, 1>(I.S, vm, vs);
+    const double den = normK * vm[1] + rhsn;
+    /* (the same values in every lane: scalar branches) */
+    const int bad = QP_UNIFORM((int)(vs[0] != 0.0)), conv = QP_UNIFORM((int)(vm[0] <= 4.0 * 2.220446049250313e-16 * den));
+    passes = pass;
+    ratio = bad ? -1.0 : ((den > 0.0) ? vm[0] / den : 0.0);
+    if (bad) { flag = 1; break; }
+    if (!conv && pass >= max_pass) { flag = 1; break; }
+    if (vm[0] == 0.0) break;
+    /* the correction this residual gives is applied in either case: the iteration converges linearly, so the iterate whose residual first meets the
+     * bound sits AT the bound, and its correction is what takes the error down to the rounding level of the solve (`passes` counts it) */
+    passes = pass + 1;
+    for (int i = tid; i < m; i += QP_T) t[i] = sgn[i] ? a.sigma()[i] * r2[i] : 0.0;
+    __syncthreads();
+    spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)t, [&](int r, double s) { xs[r] = r1[r] + s; });
+    __syncthreads();
+    if constexpr (SPARSE) { if (QP_CALL_BLOCK()) sp_solve(n, sp_arrays(V, b, slot, Dg, lds), xs); }
+    else { if (QP_CALL_BLOCK()) dense_solve(L, Dg, n, V.ld, xs, lds, V.lds_bytes); }
+    __syncthreads();
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { if (sgn[r]) w[r] = w[r] + a.sigma()[r] * (s - r2[r]); });
+    for (int j = tid; j < n; j += QP_T) u[j] = u[j] + xs[j];
+    if (conv) break;
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += QP_T) { u[j] = (flag == 0) ? (scal ? a.D()[j] * u[j] : u[j]) : 0.0; xs[j] = 0.0; }
+  for (int i = tid; i < m; i += QP_T) {
+    double wv = w[i];
+    if (scal) { wv = wv * I.s.sc_cinv; wv = wv * a.E()[i]; }
+    w[i] = (flag == 0) ? wv : 0.0;
+    v.act[i] = v.keep[i];
+  }
+  __syncthreads();
+}
+
+/* sum_k vals[pos(k)] * x[idx[k]] over the entries k in [ptr[r], ptr[r + 1]) of every row r with keep(r): G lanes per row, lane `sub` takes the entries
+ * sub, sub + G, ... in order, then the xor tree -- a gather in a fixed order (no atomics: the result does not depend on arrival order).  pos(k): where
+ * the caller's array holds entry k.  post(r, sum) consumes the result (sum = 0 for a row that is not kept). */
+template <int G, class Pos, class Keep, class Post>
+QPD void tan_gather_rows(int nrows, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ vals, const double *x,
+                         Pos pos, Keep keep, Post post) {
+  const int sub = threadIdx.x & (G - 1), grp = threadIdx.x / G;
+  for (int r0 = 0; r0 < nrows; r0 += QP_T / G) {
+    const int r = r0 + grp;
+    double acc = 0.0;
+    if (r < nrows && keep(r))
+      for (int k = ptr[r] + sub; k < ptr[r + 1]; k += G) acc = QP_FMA(vals[pos(k)], x[idx[k]], acc);
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (r < nrows && sub == 0) post(r, acc);
+  }
+}
+
+/* ---- the adjoint's right-hand side: [c D gx; E gy_J] ---- */
+QPN void adj_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, const IterShared &I) {
+  const int n = a.n, m = a.m, tid = threadIdx.x, scal = I.s.has_scaling;
+  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  const double c = I.s.sc_c;
+  for (int j = tid; j < n; j += QP_T) {
+    const double g = io.gx[on + j];
+    double r = g;
+    if (scal) { r = a.D()[j] * g; r *= c; }
+    v.rhs1[j] = r;
+  }
+  for (int i = tid; i < m; i += QP_T) {
+    const double g = (io.gy && v.sgn[i]) ? io.gy[om + i] : 0.0;
+    v.rhs2[i] = scal ? a.E()[i] * g : g;
+  }
+  __syncthreads();
+}
+
+/* ---- the tangent's right-hand side: r1 = -(dq + dQ x + dA' y), r2_i = db_i - (dA x)_i on J, formed in unscaled space from the
+ * stored solution and the caller's directions, then [c D r1; E r2].  y is the stored y of every row.  dQx / dAx are read where the caller put them
+ * (k_update_Q_A's maps): dA' y by the columns of A, dQ x by the rows of the full symmetric pattern (Qfperm: a stored lower entry stands for both
+ * positions; upper entries of the caller are in no map), dA x by the rows of A' (Atperm) -- gathers, eight lanes per column / row. ---- */
+QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, const IterShared &I) {
+  const int n = a.n, m = a.m, scal = I.s.has_scaling;
+  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  const double c = I.s.sc_c;
+  const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1, sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
+  const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr, *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
+  const double *dA = io.t_dAx ? io.t_dAx + (size_t)b * io.strideA : nullptr, *dQ = io.t_dQx ? io.t_dQx + (size_t)b * io.strideQ : nullptr;
+  const int *Atperm = a.Atperm(), *Qfperm = a.Qfperm();
+  const double *x = a.sol_x(), *y = a.sol_y();
+  double *r1 = v.r1;
+  auto all = [](int) { return true; };
+  for (int j = threadIdx.x; j < n; j += QP_T) r1[j] = io.t_dq ? io.t_dq[on + j] : 0.0;
+  __syncthreads();
+  if (dQ) {
+    tan_gather_rows<8>(n, a.Qfp(), a.Qfi(), dQ, x, [&](int k) { const int e = Qfperm[k]; return sameQ ? e : mQ[e]; }, all, [&](int r, double s) { r1[r] = r1[r] + s; });
+    __syncthreads();
+  }
+  if (dA) {
+    tan_gather_rows<8>(n, a.Ap(), a.Ai(), dA, y, [&](int k) { return sameA ? k : mA[k]; }, all, [&](int r, double s) { r1[r] = r1[r] + s; });
+    __syncthreads();
+  }
+  for (int j = threadIdx.x; j < n; j += QP_T) {
+    const double g = -r1[j];
+    double r = g;
+    if (scal) { r = a.D()[j] * g; r *= c; }
+    v.rhs1[j] = r;
+  }
+  for (int i = threadIdx.x; i < m; i += QP_T) {
+    const int sg = v.sgn[i];
+    const double *db = (sg < 0) ? io.t_dbmin : io.t_dbmax;
+    v.r2[i] = (sg && db) ? db[om + i] : 0.0; /* (inactive rows: nothing is read) */
+  }
+  __syncthreads();
+  if (dA) {
+    tan_gather_rows<8>(m, a.Atp(), a.Ati(), dA, x, [&](int k) { const int e = Atperm[k]; return sameA ? e : mA[e]; }, [&](int r) { return v.sgn[r] != 0; },
+                       [&](int r, double s) { v.r2[r] = v.r2[r] - s; });
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < m; i += QP_T) { const double g = v.r2[i]; v.rhs2[i] = scal ? a.E()[i] * g : g; }
+  __syncthreads();
+}
+
+/* One member of k_adjoint: io.tangent == 0 the adjoint, 1 the tangent.  The two differ in the right-hand side and in what they write. */
+template <int RPT>
+QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int slot, IterShared &I, char *lds) {
   const QpArrays a = qp_arrays(V, b);
   const int n = a.n, m = a.m, tid = threadIdx.x;
   const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
-  double *L = V.L + (size_t)slot * V.ld * V.nfac, *Dg = V.Dg + (size_t)slot * V.nfac;
+  const int tangent = QP_UNIFORM(io.tangent);
   __syncthreads();
   if (tid == 0) I.s = V.sc[b]; /* a copy: the factorisation's timers land in it and go nowhere */
   __syncthreads();
@@ -39,119 +260,21 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
   int flag = (status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
   int passes = 0;
   double ratio = 0.0;
-  double *u = a.delta_x(), *w = a.temp_m();
-  int *sgn = a.enter(), *keep = a.leave(), *act = a.active();
+  const SensVecs v = sens_vecs(a);
+  double *u = v.u, *w = v.w;
+  int *sgn = v.sgn;
   if (flag == 0) {
-    const int scal = I.s.has_scaling, prox = qp_prox(st, I.s);
-    const double c = I.s.sc_c, gam = I.s.gamma;
-    double *xs = a.d(), *rhs1 = a.dphi(), *r1 = a.temp_n(), *rhs2 = a.z(), *r2 = a.delta_y(), *t = a.ls_delta();
-    /* ---- the scaled right-hand side and the active set ---- */
-    for (int j = tid; j < n; j += QP_T) {
-      const double g = io.gx[on + j];
-      xs[j] = scal ? a.sol_x()[j] * a.Dinv()[j] : a.sol_x()[j];
-      double r = g;
-      if (scal) { r = a.D()[j] * g; r *= c; }
-      rhs1[j] = r; u[j] = 0.0;
-    }
-    __syncthreads();
-    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { t[r] = s; });
-    __syncthreads();
-    for (int i = tid; i < m; i += QP_T) {
-      int sg;
-      if (io.active_in) { const int64_t v = io.active_in[om + i]; sg = (v < 0) ? -1 : ((v > 0) ? 1 : 0); }
-      else { /* set_active_constraints (newton.c:122-131) on the stored solution; an equality row counts as lower */
-        double yv = a.sol_y()[i];
-        if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
-        const double axys = t[i] + 1 * (yv * a.sigma_inv()[i]);
-        const double lo = a.bmin()[i], hi = a.bmax()[i];
-        sg = (lo == hi || axys <= lo) ? -1 : ((axys >= hi) ? 1 : 0);
-      }
-      sgn[i] = sg; keep[i] = act[i]; act[i] = (sg != 0) ? 1 : 0;
-      const double g = (io.gy && sg) ? io.gy[om + i] : 0.0;
-      rhs2[i] = scal ? a.E()[i] * g : g;
-      w[i] = 0.0;
-    }
-    __syncthreads();
-    /* ---- ||K~||inf (largest absolute row sum) and ||rhs||inf ---- */
-    double vm[2] = {0.0, 0.0}, vs[1] = {0.0};
-    for (int j = tid; j < n; j += QP_T) {
-      double s = 0.0;
-      for (int k = a.Qfp()[j]; k < a.Qfp()[j + 1]; k++) s += qabs(a.Qfx()[k]);
-      for (int k = a.Ap()[j]; k < a.Ap()[j + 1]; k++) if (sgn[a.Ai()[k]]) s += qabs(a.Ax()[k]);
-      vm[0] = qmax(vm[0], s);
-      vm[1] = qmax(vm[1], qabs(rhs1[j]));
-    }
-    for (int i = tid; i < m; i += QP_T) {
-      if (!sgn[i]) continue;
-      double s = 0.0;
-      for (int k = a.Atp()[i]; k < a.Atp()[i + 1]; k++) s += qabs(a.Atx()[k]);
-      vm[0] = qmax(vm[0], s);
-      vm[1] = qmax(vm[1], qabs(rhs2[i]));
-    }
-    block_reduce<2, 0>(I.S, vm, vs);
-    const double normK = vm[0], rhsn = vm[1];
-    /* ---- F = Q~ (+ I / gamma) + A~_J' Sigma_J A~_J, factorised afresh: the slot may hold another member's factor, or this member's for another set ---- */
-    if constexpr (SPARSE) {
-      const SpArrays SP = sp_arrays(V, b, slot, Dg, lds);
-      if (QP_CALL_BLOCK()) sp_factor(V, b, n, SP, true, prox != 0, gam);
-    } else {
-      form_schur(V, b, n, L, false, true, prox != 0, gam, I.S, lds);
-      dev_factor<RPT>(V, n, L, Dg, lds, I.s.ticks_dbg);
-    }
-    /* ---- refinement on K~ z = rhs, z = [u; w] ---- */
-    for (int pass = 0;; pass++) {
-      __syncthreads();
-      spmv_rows<8>(n, a.Qfp(), a.Qfi(), a.Qfx(), (const double *)u, [&](int r, double s) { r1[r] = rhs1[r] - s; });
-      spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)u, [&](int r, double s) { r2[r] = sgn[r] ? rhs2[r] - s : 0.0; });
-      __syncthreads();
-      spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)w, [&](int r, double s) { r1[r] = r1[r] - s; });
-      __syncthreads();
-      vm[0] = 0.0; vm[1] = 0.0; vs[0] = 0.0;
-      for (int j = tid; j < n; j += QP_T) {
-        vm[0] = qmax(vm[0], qabs(r1[j])); vm[1] = qmax(vm[1], qabs(u[j]));
-        vs[0] += (double)(adj_bad(r1[j]) | adj_bad(u[j]));
-      }
-      for (int i = tid; i < m; i += QP_T) {
-        vm[0] = qmax(vm[0], qabs(r2[i])); vm[1] = qmax(vm[1], qabs(w[i]));
-        vs[0] += (double)(adj_bad(r2[i]) | adj_bad(w[i]));
-      }
-      block_reduce<2, 1>(I.S, vm, vs);
-      const double den = normK * vm[1] + rhsn;
-      /* (the same values in every lane: scalar branches) */
-      const int bad = QP_UNIFORM((int)(vs[0] != 0.0)), conv = QP_UNIFORM((int)(vm[0] <= 4.0 * 2.220446049250313e-16 * den));
-      passes = pass;
-      ratio = bad ? -1.0 : ((den > 0.0) ? vm[0] / den : 0.0);
-      if (bad) { flag = 1; break; }
-      if (!conv && pass >= io.max_pass) { flag = 1; break; }
-      if (vm[0] == 0.0) break;
-      /* the correction this residual gives is applied in either case: the iteration converges linearly, so the iterate whose residual first meets the
-       * bound sits AT the bound, and its correction is what takes the error down to the rounding level of the solve (`passes` counts it) */
-      passes = pass + 1;
-      for (int i = tid; i < m; i += QP_T) t[i] = sgn[i] ? a.sigma()[i] * r2[i] : 0.0;
-      __syncthreads();
-      spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)t, [&](int r, double s) { xs[r] = r1[r] + s; });
-      __syncthreads();
-      if constexpr (SPARSE) { if (QP_CALL_BLOCK()) sp_solve(n, sp_arrays(V, b, slot, Dg, lds), xs); }
-      else { if (QP_CALL_BLOCK()) dense_solve(L, Dg, n, V.ld, xs, lds, V.lds_bytes); }
-      __syncthreads();
-      spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { if (sgn[r]) w[r] = w[r] + a.sigma()[r] * (s - r2[r]); });
-      for (int j = tid; j < n; j += QP_T) u[j] = u[j] + xs[j];
-      if (conv) break;
-    }
-    __syncthreads();
-    /* back to the caller's scaling; the flags of the active set go back where the next solve expects them */
-    for (int j = tid; j < n; j += QP_T) { u[j] = (flag == 0) ? (scal ? a.D()[j] * u[j] : u[j]) : 0.0; xs[j] = 0.0; }
-    for (int i = tid; i < m; i += QP_T) {
-      double wv = w[i];
-      if (scal) { wv = wv * I.s.sc_cinv; wv = wv * a.E()[i]; }
-      w[i] = (flag == 0) ? wv : 0.0;
-      act[i] = keep[i];
-    }
-    __syncthreads();
+    const double normK = sens_setup<RPT>(V, a, v, io.active_in, b, slot, I, lds);
+    if (tangent) tan_rhs(V, a, v, io, b, I);
+    else adj_rhs(V, a, v, io, b, I);
+    sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, flag, passes, ratio);
   }
   /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros ---- */
   const bool ok = (flag == 0);
-  if (io.dq) for (int j = tid; j < V.n; j += QP_T) io.dq[on + j] = (ok && j < n) ? -u[j] : 0.0;
+  if (tangent) {
+    if (io.dx) for (int j = tid; j < V.n; j += QP_T) io.dx[on + j] = (ok && j < n) ? u[j] : 0.0;
+    if (io.dy) for (int i = tid; i < V.m; i += QP_T) io.dy[om + i] = (ok && i < m && sgn[i]) ? w[i] : 0.0;
+  } else if (io.dq) for (int j = tid; j < V.n; j += QP_T) io.dq[on + j] = (ok && j < n) ? -u[j] : 0.0;
   for (int i = tid; i < V.m; i += QP_T) {
     const int sg = (flag != 2 && i < m) ? sgn[i] : 0;
     const double wv = (ok && i < m) ? w[i] : 0.0;

@@ -1962,46 +1962,70 @@ extern "C" int qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io) {
  * off the work queue.  Pass cap of the refinement: 200 (a pass contracts the error by about 1 / (1 + sigma lambda), lambda the eigenvalues of
  * A_J Q^-1 A_J': sixteen digits in a handful of passes at the penalties a finished solve holds, and a member that needs more than 200 is flagged). */
 #define QPG_ADJOINT_MAX_PASS 200
-extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) {
-  NEED_SETUP(bt, "qpg_batch_adjoint_device");
-  if (!io || !io->gx) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: gx is NULL");
-  if (bt->kkt) return fail(QPG_ERR_UNSUPPORTED, bt->sparse ? "qpg_batch_adjoint_device: not available for FACTORIZE_KKT batches (sparse_kkt)" : "qpg_batch_adjoint_device: not available for FACTORIZE_KKT batches (dense KKT panel)");
-  if (bt->settings.nonconvex) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_adjoint_device: not available with nonconvex = 1");
-  if (coop_wanted(bt) || sparse_coop_wanted(bt)) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_adjoint_device: not available in coop mode (one QP on many workgroups)");
+/* what the adjoint and the tangent refuse alike: modes without the Schur factor, a solve in progress (the scalars come over for it: one transfer of
+ * B qpg_scalars per call, DESIGN.md section 13), a bad active_in */
+static int sens_refusals(qpg_batch *bt, const std::string &fn, const qpg_int *active_in) {
+  if (bt->kkt) return fail(QPG_ERR_UNSUPPORTED, fn + (bt->sparse ? ": not available for FACTORIZE_KKT batches (sparse_kkt)" : ": not available for FACTORIZE_KKT batches (dense KKT panel)"));
+  if (bt->settings.nonconvex) return fail(QPG_ERR_UNSUPPORTED, fn + ": not available with nonconvex = 1");
+  if (coop_wanted(bt) || sparse_coop_wanted(bt)) return fail(QPG_ERR_UNSUPPORTED, fn + ": not available in coop mode (one QP on many workgroups)");
   {
     std::vector<qpg_scalars> sc(bt->B);
     RT_MEMCPY_D2H(sc.data(), bt->V.sc, sc.size() * sizeof(qpg_scalars));
-    for (auto &s : sc) if (s.in_solve) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: a solve is in progress (qpg_batch_iterate left a member unfinished)");
+    for (auto &s : sc) if (s.in_solve) return fail(QPG_ERR_INVALID, fn + ": a solve is in progress (qpg_batch_iterate left a member unfinished)");
   }
   int *word = (int *)bt->V.queue; /* [0]: the work-queue head */
-  if (io->active_in && bt->m > 0) {
+  if (active_in && bt->m > 0) {
     int *bad_d = word + 1; /* (a free word of the queue block: k_solve uses [0] and [64 ..)) */
     RT_MEMSET(bad_d, 0, sizeof(int));
-    BT_LAUNCH(bt, k_adjoint_check, (int)std::min<size_t>(((size_t)bt->B * bt->m + bt->threads - 1) / bt->threads, 1024), 0, bt->V, (const int64_t *)io->active_in, bad_d);
+    BT_LAUNCH(bt, k_adjoint_check, (int)std::min<size_t>(((size_t)bt->B * bt->m + bt->threads - 1) / bt->threads, 1024), 0, bt->V, (const int64_t *)active_in, bad_d);
     if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint_check failed: " + std::string(RT_LAST_ERROR()));
     int bad = 0;
     RT_MEMCPY_D2H(&bad, bad_d, sizeof(int));
-    if (bad) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: active_in holds a value other than -1, 0, 1");
+    if (bad) return fail(QPG_ERR_INVALID, fn + ": active_in holds a value other than -1, 0, 1");
   }
-  qpg_adjoint_args ar;
-  memset(&ar, 0, sizeof(ar));
-  ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)io->active_in;
-  ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
-  ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
+  return QPG_OK;
+}
+/* the launch of k_adjoint (either mode); maps: the call reads or writes per-entry arrays in the caller's order */
+static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps) {
   ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS;
-  if (io->dQx || io->dAx) {
+  if (maps) {
     int32_t *mapA_d, *mapQ_d, *same_d;
     const int rcm = value_maps_device(bt, &mapA_d, &mapQ_d, &same_d);
     if (rcm != QPG_OK) return rcm;
     ar.mapA = mapA_d; ar.mapQ = mapQ_d; ar.same = same_d;
   }
-  RT_MEMSET(word, 0, sizeof(int));
+  RT_MEMSET((int *)bt->V.queue, 0, sizeof(int));
   const int grid = std::min(bt->B, bt->nslots);
   const size_t shm = (size_t)bt->lds_bytes;
   if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
   else BT_LAUNCH(bt, k_adjoint<1>, grid, shm, bt->V, ar);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
+}
+extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) {
+  NEED_SETUP(bt, "qpg_batch_adjoint_device");
+  if (!io || !io->gx) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: gx is NULL");
+  { const int rc = sens_refusals(bt, "qpg_batch_adjoint_device", io->active_in); if (rc != QPG_OK) return rc; }
+  qpg_adjoint_args ar;
+  memset(&ar, 0, sizeof(ar));
+  ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)io->active_in;
+  ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
+  ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
+  return sens_launch(bt, ar, io->dQx || io->dAx);
+}
+/* The tangent of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 13): the adjoint's launch in its other mode -- the same kernel, set-up,
+ * factor and refinement, on the right-hand side of a direction. */
+extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) {
+  NEED_SETUP(bt, "qpg_batch_tangent_device");
+  if (!io || (!io->dq && !io->dbmin && !io->dbmax && !io->dQx && !io->dAx)) return fail(QPG_ERR_INVALID, "qpg_batch_tangent_device: no direction (dq, dbmin, dbmax, dQx and dAx are all NULL)");
+  { const int rc = sens_refusals(bt, "qpg_batch_tangent_device", io->active_in); if (rc != QPG_OK) return rc; }
+  qpg_adjoint_args ar;
+  memset(&ar, 0, sizeof(ar));
+  ar.tangent = 1; ar.active_in = (const int64_t *)io->active_in;
+  ar.t_dq = io->dq; ar.t_dbmin = io->dbmin; ar.t_dbmax = io->dbmax; ar.t_dQx = io->dQx; ar.t_dAx = io->dAx;
+  ar.dx = io->dx; ar.dy = io->dy;
+  ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
+  return sens_launch(bt, ar, io->dQx || io->dAx);
 }
 
 extern "C" void qpg_batch_destroy(qpg_batch *bt) {

@@ -151,7 +151,7 @@ typedef struct {
                      (k_queue_order; identity before the first solve), so that the last QPs of a launch are short ones.  NULL: index order */
 } qpg_view;
 
-/* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint (include/qpalm_gfx950.h; NULL = absent) and the
+/* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint / QPGDeviceTangent (include/qpalm_gfx950.h; NULL = absent) and the
  * maps of k_update_Q_A from the device's order of the entries of Q / A back to the caller's (NULL: the same order everywhere) */
 typedef struct {
   const double *gx, *gy;      /* [B][n], [B][m] */
@@ -163,6 +163,12 @@ typedef struct {
   const int32_t *mapQ, *mapA, *same;
   int64_t strideQ, strideA;
   int32_t max_pass;           /* pass cap of the refinement */
+  /* tangent != 0: the call is qpg_batch_tangent_device (QPGDeviceTangent): the same solve on the right-hand side of the direction below, written to
+   * dx / dy; gx, gy and the five gradient outputs above are NULL then */
+  int32_t tangent;
+  const double *t_dq, *t_dbmin, *t_dbmax; /* [B][n], [B][m], [B][m]; NULL = zero */
+  const double *t_dQx, *t_dAx;            /* [B][strideQ], [B][strideA] in the caller's order of the entries; NULL = zero */
+  double *dx, *dy;                        /* [B][n], [B][m] */
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

@@ -379,6 +379,32 @@ class QpalmBatch:
         self._check(self.L.qpg_batch_adjoint_device(self.h, C.byref(io)))
         return out
 
+    TANGENT_OUT = ("dx", "dy", "active", "flag", "resid", "passes")
+
+    def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None):
+        """How the stored solutions move along one direction of the data (qpg_batch_tangent_device): dq [B][n], dbmin / dbmax [B][m], dQx [B][nnzQ_max],
+        dAx [B][nnzA_max] (the layout update_Q_A takes); None = zero, at least one must be given.  active: as for adjoint_device.  All arrays are torch
+        tensors on the context's device or raw addresses.  want: which outputs to compute, among dx [B][n], dy [B][m], active [B][m] int64 (the set
+        used), flag [B] int64 (0 done, 1 pass cap / non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses
+        to fill instead (then `want` is ignored).  Returns the dict.  The batch's state (and `epoch`) stays: x + dx, y + dy is a first-order
+        prediction of the next solution and can go straight into warm_start_device."""
+        nB, n, m = self.B, self.n, self.m
+        shapes = dict(dx=((nB, n), "float64"), dy=((nB, m), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
+                      passes=((nB,), "int64"))
+        unknown = set(out if out is not None else want) - set(shapes)
+        if unknown:
+            raise ValueError("tangent_device: unknown outputs %r" % sorted(unknown))
+        if all(v is None for v in (dq, dbmin, dbmax, dQx, dAx)):
+            raise ValueError("tangent_device: no direction (dq, dbmin, dbmax, dQx and dAx are all None)")
+        if out is None:
+            out = {k: self._empty(*shapes[k]) for k in want}
+        a = self._dev_args((dq, (nB, n), "dq", "float64"), (dbmin, (nB, m), "dbmin", "float64"), (dbmax, (nB, m), "dbmax", "float64"),
+                           (dQx, (nB, self.nnzQ), "dQx", "float64"), (dAx, (nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
+                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
+        io = capi.DeviceTangent(*a)
+        self._check(self.L.qpg_batch_tangent_device(self.h, C.byref(io)))
+        return out
+
     # -- results --------------------------------------------------------------------------------
     def info(self, b=0):
         out = Info()

@@ -9,8 +9,12 @@ are the HIP kernels behind include/qpalm_gfx950.h.
 The gradient is that of the active set at the solution; members that did not end SOLVED / DUAL_TERMINATED, or whose adjoint solve
 was flagged, get zero gradients -- `layer.last_adjoint` keeps the flags, residuals and pass counts of the latest backward call.
 
+Forward-mode AD (torch.autograd.forward_ad) goes through the tangent of the solved batch (QpalmBatch.tangent_device): one direction
+per forward pass, `layer.last_tangent` keeps its flags, residuals and pass counts.
+
 backward() differentiates the state the batch holds, so it must run before the batch is solved, warm-started or updated again (by this layer or directly):
-the batch counts those calls (`QpalmBatch.epoch`) and a backward() that comes too late raises RuntimeError instead of returning another solve's gradients."""
+the batch counts those calls (`QpalmBatch.epoch`) and a backward() that comes too late raises RuntimeError instead of returning another solve's gradients
+(the same check guards the forward-mode tangent)."""
 import torch
 
 
@@ -44,6 +48,21 @@ class _QPFunction(torch.autograd.Function):
         layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
         return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx"))
 
+    @staticmethod
+    def jvp(fctx, _layer, tq, tbmin, tbmax, tQx, tAx):
+        """forward-mode AD (torch.autograd.forward_ad): the tangent of the solved batch along the inputs' tangents (QpalmBatch.tangent_device)"""
+        layer = fctx.layer
+        bt = layer.batch
+        if bt.epoch != fctx.epoch:
+            raise RuntimeError("QPLayer.jvp: the batch was solved or updated again after this forward pass; its tangents are gone")
+        con = lambda t: None if t is None else t.detach().contiguous()
+        d = [con(t) for t in (tq, tbmin, tbmax, tQx, tAx)]
+        if all(t is None for t in d):
+            d[0] = bt._empty((bt.B, bt.n)).zero_()
+        out = bt.tangent_device(*d, want=("dx", "dy", "flag", "resid", "passes"))
+        layer.last_tangent = {k: out[k] for k in ("flag", "resid", "passes")}
+        return out["dx"], out["dy"], None
+
 
 class QPLayer(torch.nn.Module):
     """x*(q, bmin, bmax[, Qx, Ax]) of a set-up QpalmBatch as a torch module.  warm: the warm start of every forward step, as step_device takes it
@@ -51,7 +70,7 @@ class QPLayer(torch.nn.Module):
 
     def __init__(self, batch, warm=None):
         super().__init__()
-        self.batch, self.warm, self.last_adjoint = batch, warm, None
+        self.batch, self.warm, self.last_adjoint, self.last_tangent = batch, warm, None, None
 
     def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None):
         return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax)
