@@ -342,6 +342,39 @@ typedef struct {
   qpg_int         *passes;        /* out [B] */
 } QPGDeviceTangent;
 int  qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io);
+/* The polish of the solved batch: the exact solution at the final active set.  Per member, with (x, y) its stored solution and
+ * J, K as for the adjoint above (the same rule for J and its sides, the same active_in; a row with bmin = bmax always counts as lower):
+ *   K [dx; dy_J] = [-(q + Q x + A_J' y_J); b_J - A_J x],  b_i = bmin_i on a lower-active row, bmax_i on an upper-active one    (y masked by J),
+ *   candidate x^ = x + dx,  y^_i = y_i + dy_i on J and 0 elsewhere; then, on a row of J with bmin < bmax, a multiplier on the wrong side of its bound
+ *   (y^_i > 0 on a lower-active row, y^_i < 0 on an upper-active one) is set to zero.
+ * The solve is the adjoint's: the same fresh factor, refinement from zero, stopping rule, pass cap (200), resid and passes.  The verdict is taken in
+ * unscaled space with the measures of the solver's own termination test: pri(x) = max_i max(bmin_i - (A x)_i, (A x)_i - bmax_i, 0),
+ * dua(x, y) = ||Q x + q + A' y||inf, eps_pri = eps_abs + eps_rel max(||A x^||inf, ||clip(A x^, bmin, bmax)||inf), eps_dua = eps_abs + eps_rel
+ * max(||Q x^||inf, ||q||inf, ||A' y^||inf) with the batch's current settings; the clipped candidate is accepted iff
+ *   pri(x^) <= max(pri(x), eps_pri)  and  dua(x^, y^) <= max(dua(x, y), eps_dua)
+ * -- each residual is no worse than before, or still passes the termination test (a wrong active set shows up as a residual and is rejected).
+ * x, y: the candidate where accepted, the stored solution bit for bit otherwise (never zeros).  res: pri_old, dua_old, pri_new, dua_new of the member
+ * (old: the stored solution with every row's y; new: the clipped candidate; new repeats old with flag 1, and all four are 0 with flag 2, for which
+ * nothing is computed).  flag: 0 accepted; 1 the pass cap was reached or a value was not finite; 2 the member's status is not SOLVED /
+ * DUAL_TERMINATED; 3 a candidate was formed and rejected.  active_out, resid, passes: as for the adjoint.
+ * store != 0: the accepted candidates replace the members' stored solutions -- what qpg_batch_get_solution*, the adjoint, the tangent and
+ * qpg_batch_warm_start_last read.  Nothing else of a member changes: iterates, penalties, statuses, counters and QPGInfo stay and still describe the
+ * SOLVE (its residual norms and objective are those of the point the solve stopped at).  With store = 0 the call leaves exactly the state the adjoint
+ * leaves: solve -> polish -> step is bit for bit solve -> step.  Synchronous; all arrays in device memory; one deterministic launch (no floating-point
+ * atomics: two calls on the same state return the same bits).
+ * QPG_ERR_INVALID before qpg_batch_setup, while a solve is in progress, for an active_in entry outside {-1, 0, 1} and when x, y and res are all NULL
+ * and store is 0; QPG_ERR_UNSUPPORTED for FACTORIZE_KKT batches, coop mode and nonconvex settings. */
+typedef struct {
+  const qpg_int   *active_in;     /* [B][m] or NULL */
+  qpg_int          store;         /* != 0: accepted candidates become the stored solutions */
+  qpg_float       *x, *y;         /* out [B][n], [B][m]; either may be NULL */
+  qpg_float       *res;           /* out [B][4]: pri_old, dua_old, pri_new, dua_new; or NULL */
+  qpg_int         *active_out;    /* out [B][m]: the set used */
+  qpg_int         *flag;          /* out [B] */
+  qpg_float       *resid;         /* out [B] */
+  qpg_int         *passes;        /* out [B] */
+} QPGDevicePolish;
+int  qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

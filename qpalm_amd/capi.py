@@ -70,6 +70,11 @@ class DeviceTangent(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx", "active_in", "dx", "dy", "active_out", "flag", "resid", "passes")]
 
 
+class DevicePolish(C.Structure):
+    """QPGDevicePolish: the arrays of one qpg_batch_polish_device call, all addresses in device memory (0 = absent); store is a value"""
+    _fields_ = [("active_in", C.c_void_p), ("store", c_int)] + [(k, C.c_void_p) for k in ("x", "y", "res", "active_out", "flag", "resid", "passes")]
+
+
 class QpgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("qpalm_gfx950 error %d: %s" % (code, msg))
@@ -130,6 +135,8 @@ def load(path=None):
         L.qpg_batch_adjoint_device.argtypes = [C.c_void_p, C.POINTER(DeviceAdjoint)]
     if hasattr(L, "qpg_batch_tangent_device"):   # (absent from older builds of the library that tools/evidence/tangent_timing.py compares with)
         L.qpg_batch_tangent_device.argtypes = [C.c_void_p, C.POINTER(DeviceTangent)]
+    if hasattr(L, "qpg_batch_polish_device"):   # (absent from older builds of the library that tools/evidence/polish_timing.py compares with)
+        L.qpg_batch_polish_device.argtypes = [C.c_void_p, C.POINTER(DevicePolish)]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -182,7 +189,7 @@ SYMBOLS = [
     "qpg_batch_update_Q_A", "qpg_batch_update_Q_A_device", "qpg_batch_sparse_coop_info",
     "qpg_batch_update_bounds_device", "qpg_batch_update_q_device", "qpg_batch_warm_start_device", "qpg_batch_get_solution_device",
     "qpg_batch_get_status_device", "qpg_batch_step_device", "qpg_batch_get_sparse_factor", "qpg_batch_adjoint_device",
-    "qpg_batch_tangent_device",
+    "qpg_batch_tangent_device", "qpg_batch_polish_device",
 ]
 
 

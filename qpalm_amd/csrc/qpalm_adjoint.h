@@ -19,6 +19,20 @@
  * sens_setup (step 1: active set, scaled solution, ||K~||inf, the fresh factor) and sens_refine (step 2: the refinement on a given right-hand side and
  * the way back to the caller's scaling) are shared as one copy of the code; adj_rhs / tan_rhs and the outputs are what differs.
  *
+ * The polish (qpg_batch_polish_device) is the same solve once more, on the residuals of the stored solution itself:
+ *   r1 = -(q + Q x + A_J' y_J),  r2_i = b_i - (A x)_i on J,  K [dx; dy_J] = [r1; r2],  x^ = x + dx,  y^ = y + dy on J and 0 elsewhere
+ * (qpg_adjoint_args.polish; pol_rhs / pol_finish).  pol_finish clips multipliers on the wrong side of their bound, measures the candidate's residuals
+ * the way check_termination does with scaled_termination = 0, and takes the candidate iff neither residual got worse than max(old, the solve's eps).
+ * Which vector holds what in that mode (all of them scratch of the kind described below):
+ *   after sens_setup            xs = x~ (the stored x, scaled)   t[0, m) = A~ x~       u = w = 0
+ *   inside pol_rhs              r2 = y~ (every row)   rhs2 = y~ masked by J   rhs1 = Q~ x~   r1 = A~' y~, then A~_J' y~_J
+ *                               -> dua_old (rhs1, q~, r1 with every row's y) and pri_old (t) are reduced to scalars here, before anything is reused
+ *   leaving pol_rhs             rhs1 = -(q~ + Q~ x~ + A~_J' y~_J)   rhs2 = b~_J - A~_J x~   (sens_refine reads them, overwrites xs, r1, r2, t)
+ *   after sens_refine           u = dx   w = dy   (unscaled; xs = 0)
+ *   inside pol_finish           u = x^   w = y^ (clipped)   xs = x^ scaled   r2 = y^ scaled   rhs1 = Q~ x^~   r1 = A~' y^~   t[0, m) = A~ x^~
+ *   leaving pol_finish          xs = 0, as sens_refine leaves it
+ * sol_x / sol_y are read by sens_setup, pol_rhs and pol_finish and written, if at all, by the last loop of pol_finish.
+ *
  * Scratch: vectors a finished solve leaves behind and the next one rebuilds before it reads them (d, temp_n, delta_x, dphi, z, temp_m, delta_y,
  * the line-search scratch, enter / leave) and the workgroup's factor slot.  The active flags form_schur / sp_factor read are saved and put back
  * (update_sigma of a later solve may read them before its first Newton step).  x, y, the stored solution, sigma, gamma, Qx / Ax products and
@@ -246,29 +260,139 @@ QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const 
   __syncthreads();
 }
 
-/* One member of k_adjoint: io.tangent == 0 the adjoint, 1 the tangent.  The two differ in the right-hand side and in what they write. */
+/* the largest violation of a row's bounds (>= 0) and the row's value clipped to them: pri_res and z of compute_residuals at y = 0 */
+QPD double pol_viol(double ax, double lo, double hi) { return qmax(qmax(lo - ax, ax - hi), 0.0); }
+QPD double pol_clip(double ax, double lo, double hi) { return qmax(lo, qmin(ax, hi)); }
+
+/* ---- the polish's right-hand side, in the engine's scaled variables: [-(q~ + Q~ x~ + A~_J' y~_J); b~_J - A~_J x~], from xs = x~ and
+ * t = A~ x~ as sens_setup left them.  On the way the residuals of the stored solution (every row's y), unscaled as check_termination reports them:
+ * pri_old = max_i viol(A x; bmin, bmax)_i, dua_old = ||Q x + q + A' y||inf. ---- */
+QPN void pol_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, IterShared &I, double &pri_old, double &dua_old) {
+  const int n = a.n, m = a.m, tid = threadIdx.x, scal = I.s.has_scaling;
+  const double c = I.s.sc_c;
+  for (int i = tid; i < m; i += QP_T) {
+    double yv = a.sol_y()[i];
+    if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
+    v.r2[i] = yv; v.rhs2[i] = v.sgn[i] ? yv : 0.0;
+  }
+  __syncthreads();
+  spmv_rows<8>(n, a.Qfp(), a.Qfi(), a.Qfx(), (const double *)v.xs, [&](int r, double s) { v.rhs1[r] = s; });
+  spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)v.r2, [&](int r, double s) { v.r1[r] = s; });
+  __syncthreads();
+  double vm[2] = {0.0, 0.0}, vs[1] = {0.0};
+  for (int j = tid; j < n; j += QP_T) {
+    double g = v.rhs1[j] + a.q()[j]; g = g + v.r1[j];
+    vm[0] = qmax(vm[0], qabs(scal ? a.Dinv()[j] * g : g));
+  }
+  for (int i = tid; i < m; i += QP_T) {
+    const double pr = pol_viol(v.t[i], a.bmin()[i], a.bmax()[i]);
+    vm[1] = qmax(vm[1], scal ? a.Einv()[i] * pr : pr);
+  }
+  block_reduce<2, 0>(I.S, vm, vs); /* (its barriers: every read of r1 above is done before the next SpMV writes it) */
+  dua_old = scal ? vm[0] * I.s.sc_cinv : vm[0]; pri_old = vm[1];
+  spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)v.rhs2, [&](int r, double s) { v.r1[r] = s; });
+  __syncthreads();
+  for (int j = tid; j < n; j += QP_T) { double g = v.rhs1[j] + a.q()[j]; g = g + v.r1[j]; v.rhs1[j] = -g; }
+  for (int i = tid; i < m; i += QP_T) {
+    const int sg = v.sgn[i];
+    v.rhs2[i] = sg ? ((sg < 0) ? a.bmin()[i] : a.bmax()[i]) - v.t[i] : 0.0;
+  }
+  __syncthreads();
+}
+
+/* ---- the polish's candidate, verdict, outputs and store: u = dx, w = dy on entry (sens_refine; zeros when flagged).  flag: 0 accepted, 1 (unchanged, or
+ * the candidate is not finite), 2 (unchanged), 3 formed and rejected.  Only an accepted candidate is written anywhere but into scratch. ---- */
+QPN void pol_finish(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, IterShared &I, int &flag,
+                    double pri_old, double dua_old) {
+  const qpg_settings &st = *V.settings;
+  const int n = a.n, m = a.m, tid = threadIdx.x, scal = I.s.has_scaling;
+  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  double *u = v.u, *w = v.w, *xs = v.xs;
+  double pri_new = pri_old, dua_new = dua_old;
+  if (flag == 0) {
+    for (int j = tid; j < n; j += QP_T) {
+      const double xv = a.sol_x()[j] + u[j];
+      u[j] = xv; xs[j] = scal ? xv * a.Dinv()[j] : xv;
+    }
+    for (int i = tid; i < m; i += QP_T) {
+      const int sg = v.sgn[i];
+      double yv = sg ? a.sol_y()[i] + w[i] : 0.0;
+      /* the clip: a multiplier on the wrong side of its bound (y > 0 pushes on bmax, y < 0 on bmin); an equality row keeps either sign */
+      if (sg && a.bmin()[i] != a.bmax()[i] && ((sg < 0) ? (yv > 0.0) : (yv < 0.0))) yv = 0.0;
+      w[i] = yv;
+      if (scal) { yv = yv * a.Einv()[i]; yv *= I.s.sc_c; }
+      v.r2[i] = yv;
+    }
+    __syncthreads();
+    spmv_rows<8>(n, a.Qfp(), a.Qfi(), a.Qfx(), (const double *)xs, [&](int r, double s) { v.rhs1[r] = s; });
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { v.t[r] = s; });
+    spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)v.r2, [&](int r, double s) { v.r1[r] = s; });
+    __syncthreads();
+    /* compute_residuals + check_termination at the candidate, unscaled (termination.c:61-129 with scaled_termination = 0) */
+    double vm[4] = {0.0, 0.0, 0.0, 0.0}, vs[1] = {0.0};
+    for (int j = tid; j < n; j += QP_T) {
+      const double Qx = v.rhs1[j], qj = a.q()[j], Aty = v.r1[j], Dinv = scal ? a.Dinv()[j] : 1.0;
+      double g = Qx + qj; g = g + Aty;
+      vm[0] = qmax(vm[0], qabs(Dinv * g));
+      vm[1] = qmax(vm[1], qmax(qabs(Dinv * Qx), qmax(qabs(Dinv * qj), qabs(Dinv * Aty))));
+      vs[0] += (double)(adj_bad(g) | adj_bad(u[j]));
+    }
+    for (int i = tid; i < m; i += QP_T) {
+      const double ax = v.t[i], lo = a.bmin()[i], hi = a.bmax()[i], Einv = scal ? a.Einv()[i] : 1.0;
+      vm[2] = qmax(vm[2], Einv * pol_viol(ax, lo, hi));
+      vm[3] = qmax(vm[3], qmax(qabs(Einv * ax), qabs(Einv * pol_clip(ax, lo, hi))));
+      vs[0] += (double)(adj_bad(ax) | adj_bad(w[i]));
+    }
+    block_reduce<4, 1>(I.S, vm, vs);
+    const double cinv = scal ? I.s.sc_cinv : 1.0;
+    const double eps_pri = st.eps_abs + st.eps_rel * vm[3], eps_dua = st.eps_abs + st.eps_rel * (vm[1] * cinv);
+    /* (the same values in every lane: scalar branches) */
+    const int bad = QP_UNIFORM((int)(vs[0] != 0.0));
+    const int take = QP_UNIFORM((int)(vm[2] <= qmax(pri_old, eps_pri) && vm[0] * cinv <= qmax(dua_old, eps_dua)));
+    if (!bad) { pri_new = vm[2]; dua_new = vm[0] * cinv; }
+    flag = bad ? 1 : (take ? 0 : 3);
+  }
+  /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros.  Not accepted: the stored solution as it is ---- */
+  const bool ok = (flag == 0);
+  if (io.p_x) for (int j = tid; j < V.n; j += QP_T) io.p_x[on + j] = (j < n) ? (ok ? u[j] : a.sol_x()[j]) : 0.0;
+  if (io.p_y) for (int i = tid; i < V.m; i += QP_T) io.p_y[om + i] = (i < m) ? (ok ? w[i] : a.sol_y()[i]) : 0.0;
+  if (io.p_res && tid == 0) {
+    double *o = io.p_res + (size_t)4 * b;
+    o[0] = pri_old; o[1] = dua_old; o[2] = pri_new; o[3] = dua_new;
+  }
+  if (io.store && ok) {
+    for (int j = tid; j < n; j += QP_T) a.sol_x()[j] = u[j];
+    for (int i = tid; i < m; i += QP_T) a.sol_y()[i] = w[i];
+  }
+  if (flag != 2) for (int j = tid; j < n; j += QP_T) xs[j] = 0.0; /* (as sens_refine leaves it) */
+  __syncthreads();
+}
+
+/* One member of k_adjoint: the adjoint, the tangent (io.tangent) or the polish (io.polish).  They differ in the right-hand side and in what they write. */
 template <int RPT>
 QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int slot, IterShared &I, char *lds) {
   const QpArrays a = qp_arrays(V, b);
   const int n = a.n, m = a.m, tid = threadIdx.x;
   const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
-  const int tangent = QP_UNIFORM(io.tangent);
+  const int tangent = QP_UNIFORM(io.tangent), polish = QP_UNIFORM(io.polish);
   __syncthreads();
   if (tid == 0) I.s = V.sc[b]; /* a copy: the factorisation's timers land in it and go nowhere */
   __syncthreads();
   const int status = QP_UNIFORM(I.s.status);
   int flag = (status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
   int passes = 0;
-  double ratio = 0.0;
+  double ratio = 0.0, pri_old = 0.0, dua_old = 0.0;
   const SensVecs v = sens_vecs(a);
   double *u = v.u, *w = v.w;
   int *sgn = v.sgn;
   if (flag == 0) {
     const double normK = sens_setup<RPT>(V, a, v, io.active_in, b, slot, I, lds);
-    if (tangent) tan_rhs(V, a, v, io, b, I);
+    if (polish) pol_rhs(V, a, v, I, pri_old, dua_old);
+    else if (tangent) tan_rhs(V, a, v, io, b, I);
     else adj_rhs(V, a, v, io, b, I);
     sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, flag, passes, ratio);
   }
+  if (polish) pol_finish(V, a, v, io, b, I, flag, pri_old, dua_old); /* (x, y, res and the store; the outputs below that a polish has are written there) */
   /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros ---- */
   const bool ok = (flag == 0);
   if (tangent) {

@@ -2027,6 +2027,19 @@ extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *i
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
   return sens_launch(bt, ar, io->dQx || io->dAx);
 }
+/* The polish of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 14): the same launch in its third mode -- the correction of the stored
+ * solution to the exact solution at its active set, a verdict per member and, with store, the accepted candidates as the new stored solutions. */
+extern "C" int qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io) {
+  NEED_SETUP(bt, "qpg_batch_polish_device");
+  if (!io || (!io->x && !io->y && !io->res && !io->store)) return fail(QPG_ERR_INVALID, "qpg_batch_polish_device: nothing to do (x, y and res are all NULL and store is 0)");
+  { const int rc = sens_refusals(bt, "qpg_batch_polish_device", io->active_in); if (rc != QPG_OK) return rc; }
+  qpg_adjoint_args ar;
+  memset(&ar, 0, sizeof(ar));
+  ar.polish = 1; ar.store = io->store ? 1 : 0; ar.active_in = (const int64_t *)io->active_in;
+  ar.p_x = io->x; ar.p_y = io->y; ar.p_res = io->res;
+  ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
+  return sens_launch(bt, ar, false);
+}
 
 extern "C" void qpg_batch_destroy(qpg_batch *bt) {
   if (!bt) return;

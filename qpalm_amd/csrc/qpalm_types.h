@@ -151,7 +151,7 @@ typedef struct {
                      (k_queue_order; identity before the first solve), so that the last QPs of a launch are short ones.  NULL: index order */
 } qpg_view;
 
-/* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint / QPGDeviceTangent (include/qpalm_gfx950.h; NULL = absent) and the
+/* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint / QPGDeviceTangent / QPGDevicePolish (include/qpalm_gfx950.h; NULL = absent) and the
  * maps of k_update_Q_A from the device's order of the entries of Q / A back to the caller's (NULL: the same order everywhere) */
 typedef struct {
   const double *gx, *gy;      /* [B][n], [B][m] */
@@ -169,6 +169,10 @@ typedef struct {
   const double *t_dq, *t_dbmin, *t_dbmax; /* [B][n], [B][m], [B][m]; NULL = zero */
   const double *t_dQx, *t_dAx;            /* [B][strideQ], [B][strideA] in the caller's order of the entries; NULL = zero */
   double *dx, *dy;                        /* [B][n], [B][m] */
+  /* polish != 0: the call is qpg_batch_polish_device (QPGDevicePolish): the same solve on the right-hand side of the stored solution's own residuals,
+   * z = the correction; everything above except active_in / active_out / flag / passes / resid / max_pass is NULL then */
+  int32_t polish, store;                  /* store != 0: accepted candidates replace the stored solutions */
+  double *p_x, *p_y, *p_res;              /* [B][n], [B][m], [B][4] (pri_old, dua_old, pri_new, dua_new) */
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

@@ -405,6 +405,35 @@ class QpalmBatch:
         self._check(self.L.qpg_batch_tangent_device(self.h, C.byref(io)))
         return out
 
+    POLISH_OUT = ("x", "y", "res", "active", "flag", "resid", "passes")
+
+    def polish_device(self, active_in=None, store=False, want=POLISH_OUT, out=None):
+        """The exact solution at the final active set (qpg_batch_polish_device): per member one correction solve from its stored solution, a clip of
+        wrong-signed multipliers and a verdict.  active_in: as `active` of adjoint_device.  want: which outputs to compute, among x [B][n], y [B][m]
+        (the candidate where accepted, the stored solution otherwise), res [B][4] (pri_old, dua_old, pri_new, dua_new), active [B][m] int64 (the set
+        used), flag [B] int64 (0 accepted, 1 pass cap / non-finite, 2 member not solved, 3 candidate rejected), resid [B], passes [B] int64.  out: a
+        dict of tensors / addresses to fill instead (then `want` is ignored).  store: accepted candidates become the members' stored solutions (what
+        solution*, adjoint_device, tangent_device and warm_start_last read); info() still describes the solve.  Returns the dict.  `epoch` advances
+        only when store changed a member (the flags then come to the host: one small transfer)."""
+        nB, n, m = self.B, self.n, self.m
+        shapes = dict(x=((nB, n), "float64"), y=((nB, m), "float64"), res=((nB, 4), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"),
+                      resid=((nB,), "float64"), passes=((nB,), "int64"))
+        unknown = set(out if out is not None else want) - set(shapes)
+        if unknown:
+            raise ValueError("polish_device: unknown outputs %r" % sorted(unknown))
+        if out is None:
+            out = {k: self._empty(*shapes[k]) for k in want}
+        flag = out.get("flag")
+        if store and not hasattr(flag, "data_ptr"):   # the flags decide whether the stored solutions moved
+            flag = self._empty(*shapes["flag"])
+        given = dict(out, flag=flag)
+        a = self._dev_args((active_in, (nB, m), "active_in", "int64"), *[(given.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.POLISH_OUT])
+        io = capi.DevicePolish(a[0], 1 if store else 0, *a[1:])
+        self._check(self.L.qpg_batch_polish_device(self.h, C.byref(io)))
+        if store and bool((flag == 0).any()):
+            self.epoch += 1
+        return out
+
     # -- results --------------------------------------------------------------------------------
     def info(self, b=0):
         out = Info()

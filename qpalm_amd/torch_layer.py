@@ -14,7 +14,11 @@ per forward pass, `layer.last_tangent` keeps its flags, residuals and pass count
 
 backward() differentiates the state the batch holds, so it must run before the batch is solved, warm-started or updated again (by this layer or directly):
 the batch counts those calls (`QpalmBatch.epoch`) and a backward() that comes too late raises RuntimeError instead of returning another solve's gradients
-(the same check guards the forward-mode tangent)."""
+(the same check guards the forward-mode tangent).
+
+QPLayer(batch, polish=True) polishes after every forward solve (QpalmBatch.polish_device with store): the x, y it returns and the
+point backward() and jvp differentiate at are then the exact solution at the active set for every member whose polish was accepted (the others keep the
+solve's solution); `layer.last_polish` keeps the flags, the residuals before and after, and the pass counts."""
 import torch
 
 
@@ -31,6 +35,11 @@ class _QPFunction(torch.autograd.Function):
         rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm)
         if rc != 0:
             raise ValueError("QPLayer: some member's bounds were refused (bmin > bmax): %r" % out["rejected"].nonzero().flatten().tolist())
+        if layer.polish:
+            # accepted members: the exact solution at their active set, returned and stored -- backward and jvp differentiate at the stored solution
+            pol = bt.polish_device(store=True, out=dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)), flag=bt._empty((bt.B,), "int64"),
+                                                        resid=bt._empty((bt.B,)), passes=bt._empty((bt.B,), "int64")))
+            layer.last_polish = {k: pol[k] for k in ("flag", "res", "resid", "passes")}
         fctx.layer, fctx.epoch = layer, bt.epoch
         fctx.mark_non_differentiable(out["status_val"])
         return out["x"], out["y"], out["status_val"]
@@ -66,11 +75,12 @@ class _QPFunction(torch.autograd.Function):
 
 class QPLayer(torch.nn.Module):
     """x*(q, bmin, bmax[, Qx, Ax]) of a set-up QpalmBatch as a torch module.  warm: the warm start of every forward step, as step_device takes it
-    (None = cold, "last" = every member's previous solution)."""
+    (None = cold, "last" = every member's previous solution).  polish: polish every forward solve and store the result (see above)."""
 
-    def __init__(self, batch, warm=None):
+    def __init__(self, batch, warm=None, polish=False):
         super().__init__()
         self.batch, self.warm, self.last_adjoint, self.last_tangent = batch, warm, None, None
+        self.polish, self.last_polish = bool(polish), None
 
     def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None):
         return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax)
