@@ -375,6 +375,26 @@ typedef struct {
   qpg_int         *passes;        /* out [B] */
 } QPGDevicePolish;
 int  qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io);
+/* ---- the four calls above on a SUBSET of the members.  d_select: [B] qpg_int in device memory, 1 = the member takes part,
+ * 0 = it does not; NULL = every member, and the call is its counterpart above.  n_selected (host, may be NULL): how many took part.
+ * A member that is not selected is untouched: nothing is read from its rows of the input arrays (a bmin > bmax there is no error), nothing is written
+ * to its rows of the output arrays (they keep what the caller's arrays held), and nothing of its state moves -- iterates, stored solution, q, bounds,
+ * penalties, scaling, status, QPGInfo, QPGStats, the record of its raw q / bounds, its error mark.  For a selected member every array reads and
+ * writes what the full call reads and writes, bit for bit: members are independent, and the selected ones run the same kernels, handed out through
+ * the work queue (always, whatever B and the option "queue_order") in the order of the full call's queue among themselves.  Nothing selected: nothing
+ * is launched but the selection, QPG_OK.  One read of three words per call brings back the count.
+ * QPG_ERR_INVALID, before anything has changed: before qpg_batch_setup; an entry of d_select other than 0 or 1; any member (selected or not) in a
+ * solve that qpg_batch_iterate left unfinished.  QPG_ERR_UNSUPPORTED: coop and sparse coop mode; B > 131072.  Everything else as for the
+ * counterpart, its own refusals first. */
+/* The step for the selected members, in every factor mode of the one-workgroup solve.  A selected member whose bounds are refused keeps them and solves
+ * on them; QPG_ERR_INVALID at the end.  rejected: written for selected members only. */
+int  qpg_batch_step_subset_device(qpg_batch *bt, const QPGDeviceStep *io, const qpg_int *d_select, qpg_int *n_selected);
+/* Gradients of the selected members (the rows of the others, flag included, are not written). */
+int  qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const qpg_int *d_select, qpg_int *n_selected);
+/* Tangents of the selected members. */
+int  qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected);
+/* The polish of the selected members; with store, accepted candidates of selected members replace their stored solutions. */
+int  qpg_batch_polish_subset_device(qpg_batch *bt, const QPGDevicePolish *io, const qpg_int *d_select, qpg_int *n_selected);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

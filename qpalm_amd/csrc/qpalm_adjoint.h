@@ -448,6 +448,7 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
 }
 
 /* One workgroup per factor slot; the members come off the work queue (V.queue[0], zeroed by the host) as in k_solve, so B > slots works.
+ * io.list: the members of a subset call, through the same queue (everything dev_adjoint touches is the member's own or the workgroup's slot).
  * RPT = QPG_RPT_SPARSE: the sparse factor (sp_factor / sp_solve); any other value: the dense panel. */
 template <int RPT>
 __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_adjoint_args io) {
@@ -457,7 +458,8 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_a
     __syncthreads();
     if (threadIdx.x == 0) I.S.ibc[0] = atomicAdd(V.queue, 1);
     __syncthreads();
-    const int b = QP_UNIFORM(I.S.ibc[0]);
+    int b = QP_UNIFORM(I.S.ibc[0]);
+    if (b < V.B && io.list != nullptr) b = QP_UNIFORM(io.list[b]); /* a subset: the listed members, then B (k_select) */
     if (b >= V.B) break;
     dev_adjoint<RPT>(V, io, b, blockIdx.x, I, lds);
   }

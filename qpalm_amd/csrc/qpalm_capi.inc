@@ -1201,41 +1201,51 @@ extern "C" int qpg_batch_setup(qpg_batch *bt) {
 #define NEED_SETUP(bt, fn) \
   if (!(bt) || !(bt)->is_setup) return fail(QPG_ERR_INVALID, std::string(fn) + ": batch is not set up")
 
+/* The members a per-step call covers: every member (list = NULL), or the S members k_select listed in V.order (qpg_batch_*_subset_device).  The
+ * kernels that take it visit one listed member per workgroup and stop at the entry behind the last one. */
+struct Subset {
+  const int32_t *list = nullptr;
+  int S = 0;
+  int count(const qpg_batch *bt) const { return list ? S : bt->B; }
+  int blocks(const qpg_batch *bt) const { return std::min(count(bt), 2048); }
+};
+
+static int warm_start_launch(qpg_batch *bt, int has_x, int has_y, const qpg_float *d_x, const qpg_float *d_y, const Subset &sub) {
+  BT_LAUNCH(bt, k_warm_start, sub.blocks(bt), 0, bt->V, has_x, has_y, (const double *)d_x, (const double *)d_y, sub.list);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
+  return api_ok();
+}
 extern "C" int qpg_batch_warm_start(qpg_batch *bt, const qpg_float *x, const qpg_float *y) {
   NEED_SETUP(bt, "qpg_batch_warm_start");
   if (x) RT_MEMCPY_H2D(bt->V.x, x, (size_t)bt->B * bt->n * sizeof(double));
   if (y) RT_MEMCPY_H2D(bt->V.y, y, (size_t)bt->B * bt->m * sizeof(double));
-  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, x ? 1 : 0, y ? 1 : 0, (const double *)nullptr, (const double *)nullptr);
-  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
-  return api_ok();
+  return warm_start_launch(bt, x ? 1 : 0, y ? 1 : 0, nullptr, nullptr, Subset());
 }
 /* ... with x, y already in device memory: the kernel reads the caller's arrays */
 extern "C" int qpg_batch_warm_start_device(qpg_batch *bt, const qpg_float *d_x, const qpg_float *d_y) {
   NEED_SETUP(bt, "qpg_batch_warm_start_device");
-  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, d_x ? 1 : 0, d_y ? 1 : 0, (const double *)d_x, (const double *)d_y);
-  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
-  return api_ok();
+  return warm_start_launch(bt, d_x ? 1 : 0, d_y ? 1 : 0, d_x, d_y, Subset());
 }
 
 /* qpalm_warm_start with each QP's own last solution (what qpg_batch_get_solution returns), taken from HBM: the receding-
  * horizon loop of an MPC controller without the round trip of x, y through the host. */
 extern "C" int qpg_batch_warm_start_last(qpg_batch *bt) {
   NEED_SETUP(bt, "qpg_batch_warm_start_last");
-  BT_LAUNCH(bt, k_warm_start, blocks_for(bt), 0, bt->V, 2, 2, (const double *)nullptr, (const double *)nullptr);
-  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_warm_start failed: " + std::string(RT_LAST_ERROR()));
-  return api_ok();
+  return warm_start_launch(bt, 2, 2, nullptr, nullptr, Subset());
 }
 
-static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V_, int budget, int dynamic, float *ms_out) { /* dynamic: bit 0 work queue, bit 1 fresh solve */
+/* subset > 0: the launch covers the `subset` members k_select listed in V.order (always through the work queue, whatever B and "queue_order"): the
+ * list is there already, and the workgroups stop at the entry behind it */
+static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V_, int budget, int dynamic, float *ms_out, int subset = 0) { /* dynamic: bit 0 work queue, bit 1 fresh solve */
   qpg_view V = V_;
-  if (!bt->ctx->queue_order || bt->B > (1 << 17)) V.order = nullptr; /* (k_queue_order is B^2 compares: beyond 131 072 members the queue hands out the index order) */
-  const int grid = std::min(bt->B, bt->nslots);
+  if (!subset && (!bt->ctx->queue_order || bt->B > (1 << 17))) V.order = nullptr; /* (k_queue_order is B^2 compares: beyond 131 072 members the queue hands out the index order) */
+  const int grid = std::min(subset ? subset : bt->B, bt->nslots);
   if (ms_out || (dynamic & 2)) RT_MEMSET(bt->V.queue, 0, (64 + QPG_CU_KEYS) * sizeof(int)); /* work-queue head and the per-CU arrival counters
                                                                                                (coop mode: once per solve, it needs neither) */
   const int rpt = (bt->nfac + bt->threads - 1) / bt->threads;
   const size_t shm = (size_t)bt->lds_bytes;
   float ms = 0.f;
-  if ((dynamic & 1) && (dynamic & 2) && V.order) /* a fresh solve through the work queue: longest previous solve first (k_queue_order) */
+  if ((dynamic & 1) && (dynamic & 2) && V.order && !subset) /* a fresh solve through the work queue: longest previous solve first (k_queue_order) */
     BT_LAUNCH(bt, k_queue_order, (bt->B + bt->threads - 1) / bt->threads, 0, V);
   if (bt->sparse) {
     RT_TIMED_LAUNCH(ms, QP_INST(qp512, k_solve<QPG_RPT_SPARSE>), grid, QP_T, shm, V, budget, dynamic);
@@ -1258,9 +1268,9 @@ static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V_, int budget, in
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_solve failed: " + std::string(RT_LAST_ERROR()));
   return QPG_OK;
 }
-static int launch_solve(qpg_batch *bt, int budget, int dynamic) {
+static int launch_solve(qpg_batch *bt, int budget, int dynamic, int subset = 0) {
   float ms = 0.f;
-  const int rc = launch_solve_kernel(bt, bt->V, budget, dynamic, &ms);
+  const int rc = launch_solve_kernel(bt, bt->V, budget, dynamic, &ms, subset);
   if (rc != QPG_OK) return rc;
   bt->last_solve_ms = ms;
   return api_ok();
@@ -1380,7 +1390,7 @@ static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qp
   }
   return 0;
 }
-static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V, int budget, int dynamic, float *ms);
+static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V, int budget, int dynamic, float *ms, int subset);
 static int coop_solve(qpg_batch *bt) {
   qpg_view V = bt->V;
   V.offload = bt->sparse ? 1 : (bt->ctx->coop_updates ? 2 : 1); /* sparse coop mode: path updates stay on the QP's workgroup, and so does the one-workgroup path's refactorise-or-update rule */
@@ -1608,17 +1618,20 @@ extern "C" int qpg_batch_get_solution(qpg_batch *bt, qpg_float *x, qpg_float *y)
   return api_ok();
 }
 /* ... into arrays in device memory: a kernel writes them */
-extern "C" int qpg_batch_get_solution_device(qpg_batch *bt, qpg_float *d_x, qpg_float *d_y) {
-  NEED_SETUP(bt, "qpg_batch_get_solution_device");
+static int solution_to_device(qpg_batch *bt, qpg_float *d_x, qpg_float *d_y, const Subset &sub) {
   if (!d_x && !d_y) return api_ok();
-  BT_LAUNCH(bt, k_get_solution, blocks_for(bt), 0, bt->V, (double *)d_x, (double *)d_y);
+  BT_LAUNCH(bt, k_get_solution, sub.blocks(bt), 0, bt->V, (double *)d_x, (double *)d_y, sub.list);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_get_solution failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
+}
+extern "C" int qpg_batch_get_solution_device(qpg_batch *bt, qpg_float *d_x, qpg_float *d_y) {
+  NEED_SETUP(bt, "qpg_batch_get_solution_device");
+  return solution_to_device(bt, d_x, d_y, Subset());
 }
 /* info->status_val / info->iter of every QP into [B] arrays in device memory.  The QPG_ERROR marks of refused updates live on the host
  * (host_status): while there are any, they go to the device as one flag per member (the line-search scratch is idle between solves).
  * flags_in (device, [B] ints) / flags_out: see k_get_status */
-static int status_to_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_iter, const int *flags_in, qpg_int *flags_out) {
+static int status_to_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_iter, const int *flags_in, qpg_int *flags_out, const Subset &sub = Subset()) {
   if (!d_status_val && !d_iter && !flags_out) return api_ok();
   const int *err_d = nullptr;
   if (d_status_val && std::find(bt->host_status.begin(), bt->host_status.end(), (int)QPG_ERROR) != bt->host_status.end()) {
@@ -1628,7 +1641,7 @@ static int status_to_device(qpg_batch *bt, qpg_int *d_status_val, qpg_int *d_ite
     RT_MEMCPY_H2D(scratch, err.data(), err.size() * sizeof(int));
     err_d = scratch;
   }
-  BT_LAUNCH(bt, k_get_status, (bt->B + bt->threads - 1) / bt->threads, 0, bt->V, err_d, (int64_t *)d_status_val, (int64_t *)d_iter, flags_in, (int64_t *)flags_out);
+  BT_LAUNCH(bt, k_get_status, (sub.count(bt) + bt->threads - 1) / bt->threads, 0, bt->V, err_d, (int64_t *)d_status_val, (int64_t *)d_iter, flags_in, (int64_t *)flags_out, sub.list);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_get_status failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
 }
@@ -1783,13 +1796,14 @@ static int raw_need_device(qpg_batch *bt) {
 }
 
 /* after k_update_bounds: the flags come back (one int per member), refused members are marked QPG_ERROR until the next solve */
-static int bounds_flags(qpg_batch *bt, const int *bad_d, std::vector<int> &bad) {
+/* subset: the kernel wrote the flags of the listed members into zeroed scratch; a member that is not listed keeps its mark */
+static int bounds_flags(qpg_batch *bt, const int *bad_d, std::vector<int> &bad, bool subset = false) {
   bad.assign((size_t)bt->B, 0);
   RT_MEMCPY_D2H(bad.data(), bad_d, bad.size() * sizeof(int));
   int nbad = 0;
   for (size_t b = 0; b < bad.size(); b++) {
     if (bad[b]) { bt->host_status[b] = QPG_ERROR; nbad++; }
-    else if (bt->host_status[b] == QPG_ERROR) bt->host_status[b] = QPG_UNSOLVED; /* valid bounds now: qpalm_solve overwrites the status (qpalm.c:401-420) */
+    else if (!subset && bt->host_status[b] == QPG_ERROR) bt->host_status[b] = QPG_UNSOLVED; /* valid bounds now: qpalm_solve overwrites the status (qpalm.c:401-420) */
   }
   return nbad;
 }
@@ -1805,7 +1819,7 @@ extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, con
   }
   int *bad_d = (int *)bt->V.ls_idx; /* scratch: one flag per QP */
   BT_LAUNCH(bt, k_update_bounds, blocks_for(bt), 0, bt->V, bmin ? 1 : 0, bmax ? 1 : 0, bad_d, (const double *)bt->V.ls_key, (const double *)(bt->V.ls_key + m),
-            (long long)ls, (double *)nullptr, (double *)nullptr);
+            (long long)ls, (double *)nullptr, (double *)nullptr, (const int32_t *)nullptr);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_bounds failed: " + std::string(RT_LAST_ERROR()));
   std::vector<int> bad;
   const int nbad = bounds_flags(bt, bad_d, bad);
@@ -1821,17 +1835,18 @@ extern "C" int qpg_batch_update_bounds(qpg_batch *bt, const qpg_float *bmin, con
 }
 /* ... with the bounds already in device memory: the kernel reads the caller's arrays and keeps the record of the accepted raw values in
  * the device mirror; only the flags (one int per member) come back.  rejected (device, [B], or NULL): the flags for the caller */
-static int update_bounds_device(qpg_batch *bt, const qpg_float *d_bmin, const qpg_float *d_bmax, qpg_int *rejected) {
-  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)");
+static int update_bounds_device(qpg_batch *bt, const qpg_float *d_bmin, const qpg_float *d_bmax, qpg_int *rejected, const Subset &sub = Subset()) {
+  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)"); /* (a current host-side record comes over whole) */
   int *bad_d = (int *)bt->V.ls_idx;
-  BT_LAUNCH(bt, k_update_bounds, blocks_for(bt), 0, bt->V, d_bmin ? 1 : 0, d_bmax ? 1 : 0, bad_d, (const double *)d_bmin, (const double *)d_bmax,
-            (long long)bt->m, bt->raw_d_bmin(), bt->raw_d_bmax());
+  if (sub.list) RT_MEMSET(bad_d, 0, (size_t)bt->B * sizeof(int));
+  BT_LAUNCH(bt, k_update_bounds, sub.blocks(bt), 0, bt->V, d_bmin ? 1 : 0, d_bmax ? 1 : 0, bad_d, (const double *)d_bmin, (const double *)d_bmax,
+            (long long)bt->m, bt->raw_d_bmin(), bt->raw_d_bmax(), sub.list);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_bounds failed: " + std::string(RT_LAST_ERROR()));
   bt->raw_cur = 1;
   std::vector<int> bad;
-  const int nbad = bounds_flags(bt, bad_d, bad);
+  const int nbad = bounds_flags(bt, bad_d, bad, sub.list != nullptr);
   if (rejected) {
-    const int rc = status_to_device(bt, nullptr, nullptr, bad_d, rejected);
+    const int rc = status_to_device(bt, nullptr, nullptr, bad_d, rejected, sub);
     if (rc != QPG_OK) return rc;
   }
   if (nbad) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
@@ -1846,21 +1861,24 @@ extern "C" int qpg_batch_update_q(qpg_batch *bt, const qpg_float *q) { /* qpalm.
   NEED_SETUP(bt, "qpg_batch_update_q");
   if (!q) return fail(QPG_ERR_INVALID, "qpg_batch_update_q: NULL");
   RT_MEMCPY_H2D(bt->V.q, q, (size_t)bt->B * bt->n * sizeof(double));
-  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V, (const double *)nullptr, (double *)nullptr);
+  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V, (const double *)nullptr, (double *)nullptr, (const int32_t *)nullptr);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_q failed: " + std::string(RT_LAST_ERROR()));
   raw_need_host(bt);
   bt->raw_cur = 0;
   memcpy(bt->raw_q(), q, (size_t)bt->B * bt->n * sizeof(double));
   return api_ok();
 }
-extern "C" int qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q) {
-  NEED_SETUP(bt, "qpg_batch_update_q_device");
-  if (!d_q) return fail(QPG_ERR_INVALID, "qpg_batch_update_q_device: NULL");
-  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)");
-  BT_LAUNCH(bt, k_update_q, blocks_for(bt), 0, bt->V, (const double *)d_q, bt->raw_d_q());
+static int update_q_device(qpg_batch *bt, const qpg_float *d_q, const Subset &sub) {
+  if (raw_need_device(bt) != 0) return fail(QPG_ERR_ALLOC, "device allocation failed (record of the raw q and bounds)"); /* (a current host-side record comes over whole) */
+  BT_LAUNCH(bt, k_update_q, sub.blocks(bt), 0, bt->V, (const double *)d_q, bt->raw_d_q(), sub.list);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_update_q failed: " + std::string(RT_LAST_ERROR()));
   bt->raw_cur = 1;
   return api_ok();
+}
+extern "C" int qpg_batch_update_q_device(qpg_batch *bt, const qpg_float *d_q) {
+  NEED_SETUP(bt, "qpg_batch_update_q_device");
+  if (!d_q) return fail(QPG_ERR_INVALID, "qpg_batch_update_q_device: NULL");
+  return update_q_device(bt, d_q, Subset());
 }
 
 /* The maps between the device's order of the entries of A / Q and the caller's (qpg_batch::map_A / map_Q), in device memory: uploaded at the first call
@@ -1935,27 +1953,74 @@ extern "C" int qpg_batch_update_Q_A(qpg_batch *bt, const qpg_float *Qx, const qp
 /* One receding-horizon step on arrays in device memory: update_bounds -> update_q -> warm start -> solve -> get_solution -> get_status, each the
  * device form above (or qpg_batch_warm_start_last / qpg_batch_solve).  A refused member (bmin > bmax) keeps its bounds and solves on them; the call
  * then returns QPG_ERR_INVALID after the whole step has run.  Any other error ends the step where it occurs. */
-extern "C" int qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io) {
-  NEED_SETUP(bt, "qpg_batch_step_device");
-  if (!io) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: NULL");
-  if (io->warm < 0 || io->warm > 2) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: warm must be 0, 1 or 2");
-  if (io->warm == 2 && !io->warm_x && !io->warm_y) return fail(QPG_ERR_INVALID, "qpg_batch_step_device: warm = 2 needs warm_x or warm_y");
+static int step_args(const QPGDeviceStep *io, const std::string &fn) {
+  if (!io) return fail(QPG_ERR_INVALID, fn + ": NULL");
+  if (io->warm < 0 || io->warm > 2) return fail(QPG_ERR_INVALID, fn + ": warm must be 0, 1 or 2");
+  if (io->warm == 2 && !io->warm_x && !io->warm_y) return fail(QPG_ERR_INVALID, fn + ": warm = 2 needs warm_x or warm_y");
+  return QPG_OK;
+}
+/* qpg_batch_solve for the listed members: a fresh solve through the work queue on the list k_select left.  The error marks of the listed members end
+ * here, as those of every member do in qpg_batch_solve (the list comes over only while there are marks) */
+static int solve_subset(qpg_batch *bt, const Subset &sub) {
+  if (std::find(bt->host_status.begin(), bt->host_status.end(), (int)QPG_ERROR) != bt->host_status.end()) {
+    std::vector<int32_t> members((size_t)sub.S);
+    RT_MEMCPY_D2H(members.data(), sub.list, members.size() * sizeof(int32_t));
+    for (int32_t b : members) if (b >= 0 && b < bt->B) bt->host_status[b] = QPG_UNSOLVED;
+  }
+  return launch_solve(bt, 0x7fffffff, 1 | 2, sub.S);
+}
+static int step_run(qpg_batch *bt, const QPGDeviceStep *io, const Subset &sub) {
   int rc, refused = 0;
   if (io->bmin || io->bmax) {
-    rc = update_bounds_device(bt, io->bmin, io->bmax, io->rejected);
+    rc = update_bounds_device(bt, io->bmin, io->bmax, io->rejected, sub);
     if (rc == QPG_ERR_INVALID) refused = 1;
     else if (rc != QPG_OK) return rc;
   } else if (io->rejected) {
-    if ((rc = status_to_device(bt, nullptr, nullptr, nullptr, io->rejected)) != QPG_OK) return rc;
+    if ((rc = status_to_device(bt, nullptr, nullptr, nullptr, io->rejected, sub)) != QPG_OK) return rc;
   }
-  if (io->q && (rc = qpg_batch_update_q_device(bt, io->q)) != QPG_OK) return rc;
-  if (io->warm == 1 && (rc = qpg_batch_warm_start_last(bt)) != QPG_OK) return rc;
-  if (io->warm == 2 && (rc = qpg_batch_warm_start_device(bt, io->warm_x, io->warm_y)) != QPG_OK) return rc;
-  if ((rc = qpg_batch_solve(bt)) != QPG_OK) return rc;
-  if ((rc = qpg_batch_get_solution_device(bt, io->x, io->y)) != QPG_OK) return rc;
-  if ((rc = qpg_batch_get_status_device(bt, io->status_val, io->iter)) != QPG_OK) return rc;
+  if (io->q && (rc = update_q_device(bt, io->q, sub)) != QPG_OK) return rc;
+  if (io->warm == 1 && (rc = warm_start_launch(bt, 2, 2, nullptr, nullptr, sub)) != QPG_OK) return rc;
+  if (io->warm == 2 && (rc = warm_start_launch(bt, io->warm_x ? 1 : 0, io->warm_y ? 1 : 0, io->warm_x, io->warm_y, sub)) != QPG_OK) return rc;
+  if ((rc = sub.list ? solve_subset(bt, sub) : qpg_batch_solve(bt)) != QPG_OK) return rc;
+  if ((rc = solution_to_device(bt, io->x, io->y, sub)) != QPG_OK) return rc;
+  if ((rc = status_to_device(bt, io->status_val, io->iter, nullptr, nullptr, sub)) != QPG_OK) return rc;
   if (refused) return fail(QPG_ERR_INVALID, "Lower bound greater than upper bound");
   return api_ok();
+}
+extern "C" int qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io) {
+  NEED_SETUP(bt, "qpg_batch_step_device");
+  { const int rc = step_args(io, "qpg_batch_step_device"); if (rc != QPG_OK) return rc; }
+  return step_run(bt, io, Subset());
+}
+
+/* ---- subsets (DESIGN.md section 15): `d_select` ([B] qpg_int in device memory, entries 0 / 1) -> the work list of one call, in V.order (k_select).
+ * What comes back: S, and the two flags of the queue block -- one read of three words.  Refused before anything of the batch has changed: more
+ * than 2^17 members (the counting is quadratic, as k_queue_order's), an entry other than 0 / 1, a solve in progress. */
+static int select_members(qpg_batch *bt, const std::string &fn, const qpg_int *d_select, Subset &sub) {
+  if (bt->B > (1 << 17)) return fail(QPG_ERR_UNSUPPORTED, fn + ": a subset needs B <= 131072");
+  static_assert(QPG_Q_SELBAD == QPG_Q_NSEL + 1 && QPG_Q_SELBUSY == QPG_Q_NSEL + 2, "read as one block");
+  int *words = (int *)bt->V.queue + QPG_Q_NSEL;
+  RT_MEMSET(words, 0, 3 * sizeof(int));
+  BT_LAUNCH(bt, k_select, (bt->B + bt->threads - 1) / bt->threads, 0, bt->V, (const int64_t *)d_select);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_select failed: " + std::string(RT_LAST_ERROR()));
+  int got[3] = {0, 0, 0};
+  RT_MEMCPY_D2H(got, words, sizeof(got));
+  if (RT_STICKY()) return api_ok();
+  if (got[1]) return fail(QPG_ERR_INVALID, fn + ": select holds a value other than 0 or 1");
+  if (got[2]) return fail(QPG_ERR_INVALID, fn + ": a solve is in progress (qpg_batch_iterate left a member unfinished)");
+  sub.list = bt->V.order; sub.S = got[0];
+  return QPG_OK;
+}
+extern "C" int qpg_batch_step_subset_device(qpg_batch *bt, const QPGDeviceStep *io, const qpg_int *d_select, qpg_int *n_selected) {
+  NEED_SETUP(bt, "qpg_batch_step_subset_device");
+  if (!d_select) { if (n_selected) *n_selected = bt->B; return qpg_batch_step_device(bt, io); }
+  { const int rc = step_args(io, "qpg_batch_step_subset_device"); if (rc != QPG_OK) return rc; }
+  if (coop_wanted(bt) || sparse_coop_wanted(bt)) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_step_subset_device: not available in coop mode (one QP on many workgroups)");
+  Subset sub;
+  { const int rc = select_members(bt, "qpg_batch_step_subset_device", d_select, sub); if (rc != QPG_OK) return rc; }
+  if (n_selected) *n_selected = sub.S;
+  if (sub.S == 0) return api_ok();
+  return step_run(bt, io, sub);
 }
 
 /* The adjoint of the solved batch (include/qpalm_gfx950.h; the kernel: qpalm_adjoint.h).  One launch of one workgroup per factor slot; the members come
@@ -1986,7 +2051,7 @@ static int sens_refusals(qpg_batch *bt, const std::string &fn, const qpg_int *ac
   return QPG_OK;
 }
 /* the launch of k_adjoint (either mode); maps: the call reads or writes per-entry arrays in the caller's order */
-static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps) {
+static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps, const Subset &sub) {
   ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS;
   if (maps) {
     int32_t *mapA_d, *mapQ_d, *same_d;
@@ -1995,50 +2060,72 @@ static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps) {
     ar.mapA = mapA_d; ar.mapQ = mapQ_d; ar.same = same_d;
   }
   RT_MEMSET((int *)bt->V.queue, 0, sizeof(int));
-  const int grid = std::min(bt->B, bt->nslots);
+  ar.list = sub.list;
+  const int grid = std::min(sub.count(bt), bt->nslots);
   const size_t shm = (size_t)bt->lds_bytes;
   if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
   else BT_LAUNCH(bt, k_adjoint<1>, grid, shm, bt->V, ar);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
 }
-extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) {
-  NEED_SETUP(bt, "qpg_batch_adjoint_device");
-  if (!io || !io->gx) return fail(QPG_ERR_INVALID, "qpg_batch_adjoint_device: gx is NULL");
-  { const int rc = sens_refusals(bt, "qpg_batch_adjoint_device", io->active_in); if (rc != QPG_OK) return rc; }
+/* what the three subset forms do before their launch, after the refusals of the full form: the list.  1: nothing is selected, the call is over */
+static int sens_select(qpg_batch *bt, const std::string &fn, const qpg_int *d_select, qpg_int *n_selected, Subset &sub, int &rc) {
+  rc = QPG_OK;
+  if (!d_select) { if (n_selected) *n_selected = bt->B; return 0; }
+  if ((rc = select_members(bt, fn, d_select, sub)) != QPG_OK) return 1;
+  if (n_selected) *n_selected = sub.S;
+  if (sub.S == 0) { rc = api_ok(); return 1; }
+  return 0;
+}
+extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) { return qpg_batch_adjoint_subset_device(bt, io, nullptr, nullptr); }
+extern "C" int qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const qpg_int *d_select, qpg_int *n_selected) {
+  const std::string fn = d_select ? "qpg_batch_adjoint_subset_device" : "qpg_batch_adjoint_device";
+  NEED_SETUP(bt, fn);
+  if (!io || !io->gx) return fail(QPG_ERR_INVALID, fn + ": gx is NULL");
+  { const int rc = sens_refusals(bt, fn, io->active_in); if (rc != QPG_OK) return rc; }
+  Subset sub;
+  { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
   qpg_adjoint_args ar;
   memset(&ar, 0, sizeof(ar));
   ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)io->active_in;
   ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
-  return sens_launch(bt, ar, io->dQx || io->dAx);
+  return sens_launch(bt, ar, io->dQx || io->dAx, sub);
 }
 /* The tangent of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 13): the adjoint's launch in its other mode -- the same kernel, set-up,
  * factor and refinement, on the right-hand side of a direction. */
-extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) {
-  NEED_SETUP(bt, "qpg_batch_tangent_device");
-  if (!io || (!io->dq && !io->dbmin && !io->dbmax && !io->dQx && !io->dAx)) return fail(QPG_ERR_INVALID, "qpg_batch_tangent_device: no direction (dq, dbmin, dbmax, dQx and dAx are all NULL)");
-  { const int rc = sens_refusals(bt, "qpg_batch_tangent_device", io->active_in); if (rc != QPG_OK) return rc; }
+extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) { return qpg_batch_tangent_subset_device(bt, io, nullptr, nullptr); }
+extern "C" int qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected) {
+  const std::string fn = d_select ? "qpg_batch_tangent_subset_device" : "qpg_batch_tangent_device";
+  NEED_SETUP(bt, fn);
+  if (!io || (!io->dq && !io->dbmin && !io->dbmax && !io->dQx && !io->dAx)) return fail(QPG_ERR_INVALID, fn + ": no direction (dq, dbmin, dbmax, dQx and dAx are all NULL)");
+  { const int rc = sens_refusals(bt, fn, io->active_in); if (rc != QPG_OK) return rc; }
+  Subset sub;
+  { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
   qpg_adjoint_args ar;
   memset(&ar, 0, sizeof(ar));
   ar.tangent = 1; ar.active_in = (const int64_t *)io->active_in;
   ar.t_dq = io->dq; ar.t_dbmin = io->dbmin; ar.t_dbmax = io->dbmax; ar.t_dQx = io->dQx; ar.t_dAx = io->dAx;
   ar.dx = io->dx; ar.dy = io->dy;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
-  return sens_launch(bt, ar, io->dQx || io->dAx);
+  return sens_launch(bt, ar, io->dQx || io->dAx, sub);
 }
 /* The polish of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 14): the same launch in its third mode -- the correction of the stored
  * solution to the exact solution at its active set, a verdict per member and, with store, the accepted candidates as the new stored solutions. */
-extern "C" int qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io) {
-  NEED_SETUP(bt, "qpg_batch_polish_device");
-  if (!io || (!io->x && !io->y && !io->res && !io->store)) return fail(QPG_ERR_INVALID, "qpg_batch_polish_device: nothing to do (x, y and res are all NULL and store is 0)");
-  { const int rc = sens_refusals(bt, "qpg_batch_polish_device", io->active_in); if (rc != QPG_OK) return rc; }
+extern "C" int qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io) { return qpg_batch_polish_subset_device(bt, io, nullptr, nullptr); }
+extern "C" int qpg_batch_polish_subset_device(qpg_batch *bt, const QPGDevicePolish *io, const qpg_int *d_select, qpg_int *n_selected) {
+  const std::string fn = d_select ? "qpg_batch_polish_subset_device" : "qpg_batch_polish_device";
+  NEED_SETUP(bt, fn);
+  if (!io || (!io->x && !io->y && !io->res && !io->store)) return fail(QPG_ERR_INVALID, fn + ": nothing to do (x, y and res are all NULL and store is 0)");
+  { const int rc = sens_refusals(bt, fn, io->active_in); if (rc != QPG_OK) return rc; }
+  Subset sub;
+  { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
   qpg_adjoint_args ar;
   memset(&ar, 0, sizeof(ar));
   ar.polish = 1; ar.store = io->store ? 1 : 0; ar.active_in = (const int64_t *)io->active_in;
   ar.p_x = io->x; ar.p_y = io->y; ar.p_res = io->res;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
-  return sens_launch(bt, ar, false);
+  return sens_launch(bt, ar, false, sub);
 }
 
 extern "C" void qpg_batch_destroy(qpg_batch *bt) {

@@ -290,11 +290,15 @@ __global__ __launch_bounds__(QP_T) void k_lobpcg(qpg_view V) {
   }
 }
 
+/* The member a per-step kernel visits in pass h of its loop over the batch: h itself, or list[h] of a subset call (qpg_batch_step_subset_device) -- the
+ * list k_select leaves in qpg_view.order: the selected members, then B, on which the loops stop.  Members that are not listed are neither read nor written. */
+QPD int qp_listed(const int32_t *list, int h) { return list ? QP_UNIFORM(list[h]) : h; }
+
 /* src_x / src_y: the caller's own arrays in device memory ([B][n] / [B][m], qpg_batch_warm_start_device), read here instead of a copy the host
  * placed in x / y; NULL = the host placed them (has_x / has_y = 1) or they are not needed */
-__global__ __launch_bounds__(QP_T) void k_warm_start(qpg_view V, int has_x, int has_y, const double *src_x, const double *src_y) {
+__global__ __launch_bounds__(QP_T) void k_warm_start(qpg_view V, int has_x, int has_y, const double *src_x, const double *src_y, const int32_t *list) {
   __shared__ IterShared I;
-  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+  for (int h = blockIdx.x, b; h < V.B && (b = qp_listed(list, h)) < V.B; h += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     __syncthreads();
     if (threadIdx.x == 0) I.s = V.sc[b];
@@ -372,6 +376,45 @@ __global__ __launch_bounds__(QP_T) void k_queue_order(qpg_view V) {
   if (b < V.B) V.order[rank] = b;
 }
 
+/* The work list of a subset call (qpg_batch_*_subset_device): select[b] = 1 puts member b on it.  The S selected members go to order[0, S) in
+ * k_queue_order's order among themselves (descending kernel time of the previous solve, ties by index: the same counting, a member that is not selected
+ * counts for nobody), and order[S, B) = B: the value on which k_solve, k_adjoint and the per-step kernels stop.  Every thread counts S and the selected
+ * members before its own along the way, so a member that is not selected knows its place behind them.  queue[QPG_Q_NSEL] = S; queue[QPG_Q_SELBAD] = 1
+ * (zeroed by the host): an entry of `select` is neither 0 nor 1, and the caller refuses the call; queue[QPG_Q_SELBUSY] = 1 (likewise): a member --
+ * selected or not -- is in a solve.  B <= 2^17, like k_queue_order (the host refuses more). */
+__global__ __launch_bounds__(QP_T) void k_select(qpg_view V, const int64_t *select) {
+  __shared__ long long cost[QP_T];
+  const long long out = -0x7fffffffffffffffLL - 1; /* a member that is not selected: below every cost, equal to none */
+  const int b = blockIdx.x * QP_T + threadIdx.x;
+  const int64_t sv = (b < V.B) ? select[b] : 0;
+  const bool sel = (sv == 1);
+  const long long mine = sel ? V.sc[b].ticks_total : 0;
+  if (b < V.B) {
+    if (sv != 0 && sv != 1) V.queue[QPG_Q_SELBAD] = 1; /* (every writer stores the same value) */
+    if (V.sc[b].in_solve) V.queue[QPG_Q_SELBUSY] = 1;
+  }
+  int rank = 0, nsel = 0, before = 0;
+  for (int c0 = 0; c0 < V.B; c0 += QP_T) {
+    __syncthreads();
+    const int c = c0 + threadIdx.x;
+    cost[threadIdx.x] = (c < V.B && select[c] == 1) ? V.sc[c].ticks_total : out;
+    __syncthreads();
+    const int lim = (V.B - c0 < QP_T) ? (V.B - c0) : QP_T;
+    for (int k = 0; k < lim; k++) {
+      const long long ck = cost[k];
+      const int s = (ck != out) ? 1 : 0;
+      nsel += s;
+      before += (s && c0 + k < b) ? 1 : 0;
+      rank += (ck > mine || (ck == mine && c0 + k < b)) ? 1 : 0;
+    }
+  }
+  if (b < V.B) {
+    if (sel) V.order[rank] = b;
+    else V.order[nsel + (b - before)] = V.B; /* b - before: the members before b that are not selected */
+    if (b == 0) V.queue[QPG_Q_NSEL] = nsel;
+  }
+}
+
 /* The persistent solver: workgroup `blockIdx.x` owns factor slot `blockIdx.x` and pulls QPs either
  * statically (b = blockIdx.x, resumable, needs B <= grid) or from an atomic work queue (dynamic & 1).  dynamic & 2: a
  * fresh qpalm_solve -- QPs whose previous solve has finished start over. */
@@ -401,9 +444,9 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_solve(qpg_view V, int bud
  * (qpg_batch_update_bounds_device) passes the caller's own [B][m] arrays.  Validation (bmin <= bmax, qpalm.c:806-817) happens here too: bad[b] = 1
  * leaves the QP's bounds untouched.  raw_min / raw_max ([B][m], or NULL): the mirror of the accepted raw bounds (qpg_batch::raw_d) is filled here. */
 __global__ __launch_bounds__(QP_T) void k_update_bounds(qpg_view V, int has_bmin, int has_bmax, int *bad, const double *src_min, const double *src_max,
-                                                        long long stride, double *raw_min, double *raw_max) {
+                                                        long long stride, double *raw_min, double *raw_max, const int32_t *list) {
   __shared__ int s_bad;
-  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+  for (int h = blockIdx.x, b; h < V.B && (b = qp_listed(list, h)) < V.B; h += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     const double *smin = src_min + (size_t)b * stride, *smax = src_max + (size_t)b * stride;
     int mine = 0;
@@ -429,10 +472,10 @@ __global__ __launch_bounds__(QP_T) void k_update_bounds(qpg_view V, int has_bmin
 
 /* qpalm_update_q, device part (qpalm.c:829-871).  src = NULL: the host wrote the raw q into place; else the caller's own [B][n] array in device
  * memory (qpg_batch_update_q_device), copied into place here first, and into raw_q (the mirror of the raw values, qpg_batch::raw_d) */
-__global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V, const double *src, double *raw_q) {
+__global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V, const double *src, double *raw_q, const int32_t *list) {
   __shared__ IterShared I;
   const qpg_settings &st = *V.settings;
-  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+  for (int h = blockIdx.x, b; h < V.B && (b = qp_listed(list, h)) < V.B; h += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     __syncthreads();
     if (threadIdx.x == 0) I.s = V.sc[b];
@@ -481,8 +524,8 @@ __global__ __launch_bounds__(QP_T) void k_update_q(qpg_view V, const double *src
 
 /* qpg_batch_get_solution_device: the stored solutions into the caller's [B][n] / [B][m] arrays (either may be NULL); entries beyond a member's own
  * n / m are written as zeros */
-__global__ __launch_bounds__(QP_T) void k_get_solution(qpg_view V, double *out_x, double *out_y) {
-  for (int b = blockIdx.x; b < V.B; b += gridDim.x) {
+__global__ __launch_bounds__(QP_T) void k_get_solution(qpg_view V, double *out_x, double *out_y, const int32_t *list) {
+  for (int h = blockIdx.x, b; h < V.B && (b = qp_listed(list, h)) < V.B; h += gridDim.x) {
     const QpArrays a = qp_arrays(V, b);
     if (out_x) for (int j = threadIdx.x; j < V.n; j += QP_T) out_x[(size_t)b * V.n + j] = (j < a.n) ? a.sol_x()[j] : 0.0;
     if (out_y) for (int i = threadIdx.x; i < V.m; i += QP_T) out_y[(size_t)b * V.m + i] = (i < a.m) ? a.sol_y()[i] : 0.0;
@@ -491,9 +534,12 @@ __global__ __launch_bounds__(QP_T) void k_get_solution(qpg_view V, double *out_x
 
 /* qpg_batch_get_status_device: info->status_val and info->iter of every QP into the caller's [B] arrays of 64-bit integers, one thread per QP.
  * err ([B], or NULL): members the host marked QPG_ERROR (a refused update) read as such.  flags_out ([B], or NULL) = flags_in[b] != 0
- * (0 everywhere without flags_in): the "rejected" array of qpg_batch_step_device.  Any output may be NULL. */
-__global__ __launch_bounds__(QP_T) void k_get_status(qpg_view V, const int *err, int64_t *status_val, int64_t *iter, const int *flags_in, int64_t *flags_out) {
-  for (int b = blockIdx.x * QP_T + threadIdx.x; b < V.B; b += gridDim.x * QP_T) {
+ * (0 everywhere without flags_in): the "rejected" array of qpg_batch_step_device.  Any output may be NULL.  list: see qp_listed (one thread per entry). */
+__global__ __launch_bounds__(QP_T) void k_get_status(qpg_view V, const int *err, int64_t *status_val, int64_t *iter, const int *flags_in, int64_t *flags_out,
+                                                     const int32_t *list) {
+  for (int h = blockIdx.x * QP_T + threadIdx.x; h < V.B; h += gridDim.x * QP_T) {
+    const int b = list ? list[h] : h;
+    if (b >= V.B) continue;
     if (status_val) status_val[b] = (err && err[b]) ? QPG_ERROR : V.sc[b].status;
     if (iter) iter[b] = V.sc[b].iter;
     if (flags_out) flags_out[b] = (flags_in && flags_in[b]) ? 1 : 0;

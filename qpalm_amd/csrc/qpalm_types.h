@@ -146,10 +146,16 @@ typedef struct {
   double *sp_co_wv;         /* [B][sp_co_G][wavefronts x sp_gpw][n] the work vectors of those workgroups (zero outside of use); NULL without sparse coop mode */
   qpg_scalars *sc; /* [B] */
   qpg_settings *settings; /* [1] */
-  int32_t *queue; /* [64 + QPG_CU_KEYS]: [0] work-queue head; [64 + key] workgroups that have arrived on compute unit `key` in this launch */
+  int32_t *queue; /* [64 + QPG_CU_KEYS]: [0] work-queue head; [64 + key] workgroups that have arrived on compute unit `key` in this launch.
+                     Words [1, 64) are free for the host's calls between launches: [1] the "bad active_in" flag of the sensitivity calls
+                     (sens_refusals), [QPG_Q_NSEL], [QPG_Q_SELBAD] and [QPG_Q_SELBUSY] the results of k_select */
   int32_t *order; /* [B] the work queue hands out order[0], order[1], ...: the members by the kernel time of their PREVIOUS solve, longest first
-                     (k_queue_order; identity before the first solve), so that the last QPs of a launch are short ones.  NULL: index order */
+                     (k_queue_order; identity before the first solve), so that the last QPs of a launch are short ones.  NULL: index order.
+                     A subset call (k_select) leaves the S selected members in that order in [0, S) and B, on which a workgroup stops, in [S, B) */
 } qpg_view;
+#define QPG_Q_NSEL 2     /* queue word: S, the number of selected members (k_select) */
+#define QPG_Q_SELBAD 3   /* queue word, zeroed by the host before k_select: 1 = `select` holds a value other than 0 / 1 */
+#define QPG_Q_SELBUSY 4  /* queue word, zeroed by the host before k_select: 1 = a member is in a solve (qpg_scalars.in_solve) */
 
 /* arguments of k_adjoint (qpalm_adjoint.h), all in device memory: the arrays of QPGDeviceAdjoint / QPGDeviceTangent / QPGDevicePolish (include/qpalm_gfx950.h; NULL = absent) and the
  * maps of k_update_Q_A from the device's order of the entries of Q / A back to the caller's (NULL: the same order everywhere) */
@@ -173,6 +179,9 @@ typedef struct {
    * z = the correction; everything above except active_in / active_out / flag / passes / resid / max_pass is NULL then */
   int32_t polish, store;                  /* store != 0: accepted candidates replace the stored solutions */
   double *p_x, *p_y, *p_res;              /* [B][n], [B][m], [B][4] (pri_old, dua_old, pri_new, dua_new) */
+  /* list != NULL: the call covers a subset (qpg_batch_*_subset_device): the queue hands out list[0], list[1], ... and a workgroup stops at the first
+   * entry >= B (qpg_view.order as k_select leaves it); members that are not listed are neither read nor written */
+  const int32_t *list;
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

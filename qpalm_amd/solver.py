@@ -317,17 +317,33 @@ class QpalmBatch:
 
     STEP_OUT = ("x", "y", "status_val", "iter", "rejected")
 
-    def step_device(self, bmin=None, bmax=None, q=None, warm="last", out=None):
+    def _subset_call(self, name, io, select):
+        """the full call (select is None), or its subset form with select ([B] int64 tensor on the batch's device, entries 0 / 1, validated like every
+        other array); returns (rc, n_selected)"""
+        if select is None:
+            return getattr(self.L, "qpg_batch_%s_device" % name)(self.h, C.byref(io)), self.B
+        if isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr"):
+            raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
+        sel, = self._dev_args((select, (self.B,), "select", "int64"))
+        cnt = capi.c_int(0)
+        rc = getattr(self.L, "qpg_batch_%s_subset_device" % name)(self.h, C.byref(io), sel, C.byref(cnt))
+        return rc, int(cnt.value)
+
+    def step_device(self, bmin=None, bmax=None, q=None, warm="last", out=None, select=None):
         """One receding-horizon step without the host (qpg_batch_step_device): new bounds / q (None = unchanged), warm start ("last" = every QP's own
         last solution, None = none, (x, y) = given arrays, one of which may be None), solve, and the results written in device memory.  All arrays are
         torch tensors on the context's device or raw addresses.  out: a dict with any of the keys x, y, status_val, iter, rejected (absent or None =
         not wanted); without it all five are allocated.  Returns (rc, out): rc = 0, or -2 (QPG_ERR_INVALID) when some member's bounds were refused --
-        the step has run all the same, that member on its old bounds, and out["rejected"] says which."""
+        the step has run all the same, that member on its old bounds, and out["rejected"] says which.
+        select: None, or a [B] int64 tensor of 0 / 1 on the batch's device: only the members with 1 take the step (qpg_batch_step_subset_device,
+        DESIGN.md section 15); the others are untouched -- their state, and their rows of every `out` array, which keep what they held (arrays
+        allocated here hold uninitialised memory there).  With select the returned dict also holds n_selected (an int: how many members took the
+        step; the key is ignored when the dict is handed in again); an entry other than 0 / 1, or a solve in progress, raises QpgError (-2)."""
         self.epoch += 1
         if out is None:
             out = dict(x=self._empty((self.B, self.n)), y=self._empty((self.B, self.m)), status_val=self._empty((self.B,), "int64"),
                        iter=self._empty((self.B,), "int64"), rejected=self._empty((self.B,), "int64"))
-        unknown = set(out) - set(self.STEP_OUT)
+        unknown = set(out) - set(self.STEP_OUT) - {"n_selected"}
         if unknown:
             raise ValueError("out: unknown keys %r" % sorted(unknown))
         if warm is None:
@@ -348,25 +364,28 @@ class QpalmBatch:
                            (out.get("status_val"), (nB,), "out status_val", "int64"), (out.get("iter"), (nB,), "out iter", "int64"),
                            (out.get("rejected"), (nB,), "out rejected", "int64"))
         io = capi.DeviceStep(a[0], a[1], a[2], a[3], a[4], mode, a[5], a[6], a[7], a[8], a[9])
-        rc = self.L.qpg_batch_step_device(self.h, C.byref(io))
-        if rc not in (0, -2):
+        rc, cnt = self._subset_call("step", io, select)
+        if rc not in (0, -2) or (rc == -2 and select is not None and b"Lower bound" not in self.L.qpg_last_error()):
             self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
         return rc, out
 
     ADJOINT_OUT = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
 
-    def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None):
+    def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None):
         """Gradients of a loss through the stored solutions (qpg_batch_adjoint_device): gx = dl/dx [B][n], gy = dl/dy [B][m] or None, active = the active
         set to differentiate at ([B][m] int64: -1 lower, +1 upper, 0 inactive) or None for the engine's own test on the stored solution.  All arrays
         are torch tensors on the context's device or raw addresses.  want: which outputs to compute, among dq [B][n], dbmin / dbmax [B][m],
         dQx [B][nnzQ_max], dAx [B][nnzA_max] (the layout update_Q_A takes), active [B][m] int64 (the set used), flag [B] int64 (0 done, 1 pass cap /
         non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses to fill instead (then `want` is ignored).
-        Returns the dict."""
+        Returns the dict.  select: as for step_device -- only the members with 1 are differentiated (qpg_batch_adjoint_subset_device); the rows of the
+        others in every output, flag included, keep what they held, and the dict gains n_selected."""
         nB, n, m = self.B, self.n, self.m
         shapes = dict(dq=((nB, n), "float64"), dbmin=((nB, m), "float64"), dbmax=((nB, m), "float64"), dQx=((nB, self.nnzQ), "float64"),
                       dAx=((nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
                       passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes)
+        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
         if unknown:
             raise ValueError("adjoint_device: unknown outputs %r" % sorted(unknown))
         if gx is None:
@@ -376,22 +395,26 @@ class QpalmBatch:
         a = self._dev_args((gx, (nB, n), "gx", "float64"), (gy, (nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
                            *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
         io = capi.DeviceAdjoint(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11])
-        self._check(self.L.qpg_batch_adjoint_device(self.h, C.byref(io)))
+        rc, cnt = self._subset_call("adjoint", io, select)
+        self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
         return out
 
     TANGENT_OUT = ("dx", "dy", "active", "flag", "resid", "passes")
 
-    def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None):
+    def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None):
         """How the stored solutions move along one direction of the data (qpg_batch_tangent_device): dq [B][n], dbmin / dbmax [B][m], dQx [B][nnzQ_max],
         dAx [B][nnzA_max] (the layout update_Q_A takes); None = zero, at least one must be given.  active: as for adjoint_device.  All arrays are torch
         tensors on the context's device or raw addresses.  want: which outputs to compute, among dx [B][n], dy [B][m], active [B][m] int64 (the set
         used), flag [B] int64 (0 done, 1 pass cap / non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses
         to fill instead (then `want` is ignored).  Returns the dict.  The batch's state (and `epoch`) stays: x + dx, y + dy is a first-order
-        prediction of the next solution and can go straight into warm_start_device."""
+        prediction of the next solution and can go straight into warm_start_device.  select: as for adjoint_device
+        (qpg_batch_tangent_subset_device)."""
         nB, n, m = self.B, self.n, self.m
         shapes = dict(dx=((nB, n), "float64"), dy=((nB, m), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
                       passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes)
+        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
         if unknown:
             raise ValueError("tangent_device: unknown outputs %r" % sorted(unknown))
         if all(v is None for v in (dq, dbmin, dbmax, dQx, dAx)):
@@ -402,23 +425,27 @@ class QpalmBatch:
                            (dQx, (nB, self.nnzQ), "dQx", "float64"), (dAx, (nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
                            *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
         io = capi.DeviceTangent(*a)
-        self._check(self.L.qpg_batch_tangent_device(self.h, C.byref(io)))
+        rc, cnt = self._subset_call("tangent", io, select)
+        self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
         return out
 
     POLISH_OUT = ("x", "y", "res", "active", "flag", "resid", "passes")
 
-    def polish_device(self, active_in=None, store=False, want=POLISH_OUT, out=None):
+    def polish_device(self, active_in=None, store=False, want=POLISH_OUT, out=None, select=None):
         """The exact solution at the final active set (qpg_batch_polish_device): per member one correction solve from its stored solution, a clip of
         wrong-signed multipliers and a verdict.  active_in: as `active` of adjoint_device.  want: which outputs to compute, among x [B][n], y [B][m]
         (the candidate where accepted, the stored solution otherwise), res [B][4] (pri_old, dua_old, pri_new, dua_new), active [B][m] int64 (the set
         used), flag [B] int64 (0 accepted, 1 pass cap / non-finite, 2 member not solved, 3 candidate rejected), resid [B], passes [B] int64.  out: a
         dict of tensors / addresses to fill instead (then `want` is ignored).  store: accepted candidates become the members' stored solutions (what
         solution*, adjoint_device, tangent_device and warm_start_last read); info() still describes the solve.  Returns the dict.  `epoch` advances
-        only when store changed a member (the flags then come to the host: one small transfer)."""
+        only when store changed a member (the flags then come to the host: one small transfer).  select: as for adjoint_device
+        (qpg_batch_polish_subset_device): only selected members are polished and, with store, replaced; only their flags count for `epoch`."""
         nB, n, m = self.B, self.n, self.m
         shapes = dict(x=((nB, n), "float64"), y=((nB, m), "float64"), res=((nB, 4), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"),
                       resid=((nB,), "float64"), passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes)
+        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
         if unknown:
             raise ValueError("polish_device: unknown outputs %r" % sorted(unknown))
         if out is None:
@@ -429,9 +456,12 @@ class QpalmBatch:
         given = dict(out, flag=flag)
         a = self._dev_args((active_in, (nB, m), "active_in", "int64"), *[(given.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.POLISH_OUT])
         io = capi.DevicePolish(a[0], 1 if store else 0, *a[1:])
-        self._check(self.L.qpg_batch_polish_device(self.h, C.byref(io)))
-        if store and bool((flag == 0).any()):
+        rc, cnt = self._subset_call("polish", io, select)
+        self._check(rc)
+        if store and bool(((flag == 0) if select is None else (flag == 0) & (select != 0)).any()):
             self.epoch += 1
+        if select is not None:
+            out["n_selected"] = cnt
         return out
 
     # -- results --------------------------------------------------------------------------------

@@ -18,29 +18,44 @@ the batch counts those calls (`QpalmBatch.epoch`) and a backward() that comes to
 
 QPLayer(batch, polish=True) polishes after every forward solve (QpalmBatch.polish_device with store): the x, y it returns and the
 point backward() and jvp differentiate at are then the exact solution at the active set for every member whose polish was accepted (the others keep the
-solve's solution); `layer.last_polish` keeps the flags, the residuals before and after, and the pass counts."""
+solve's solution); `layer.last_polish` keeps the flags, the residuals before and after, and the pass counts.
+
+layer(q, ..., select=s) with s a [B] int64 tensor of 0 / 1 steps only the members with 1 (QpalmBatch.step_device(select=s)).  x, y and
+status are still those of every member: the rows of the others are their stored solutions and statuses from before.  backward and jvp pass the same
+select on, so those members cost nothing there and get zero gradients and tangents; with polish=True only the selected members are polished.  The rows of
+`last_adjoint`, `last_tangent` and `last_polish` (flag, resid, passes, res) mean something for the selected members only; the others read zero.  Input rows
+of members that are not selected are not read at all.  A subset forward needs every output row it returns to exist, so call it after a full forward or solve."""
 import torch
 
 
 class _QPFunction(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, layer, q, bmin, bmax, Qx, Ax):
+    def forward(fctx, layer, q, bmin, bmax, Qx, Ax, select=None):
         bt = layer.batch
         if (Qx is None) != (Ax is None):
             raise ValueError("Qx and Ax: give both or neither (update_Q_A takes both)")
+        if Qx is not None and select is not None:
+            raise ValueError("select: update_Q_A rebuilds every member, so Qx / Ax cannot be combined with a subset")
         if Qx is not None:
             a, b = bt._dev_args((Qx.detach(), (bt.B, bt.nnzQ), "Qx", "float64"), (Ax.detach(), (bt.B, bt.nnzA), "Ax", "float64"))
             bt.update_Q_A_device(a.value, b.value)
         det = lambda t: None if t is None else t.detach()
-        rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm)
+        if select is None:
+            rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm)
+        else:
+            # the step writes the selected rows only: x, y and the statuses of every member are read afterwards
+            rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm, out=dict(rejected=bt._empty((bt.B,), "int64").zero_()), select=select)
+            out["x"], out["y"] = bt.solution_device()
+            out["status_val"], _ = bt.status_device()
         if rc != 0:
             raise ValueError("QPLayer: some member's bounds were refused (bmin > bmax): %r" % out["rejected"].nonzero().flatten().tolist())
         if layer.polish:
             # accepted members: the exact solution at their active set, returned and stored -- backward and jvp differentiate at the stored solution
-            pol = bt.polish_device(store=True, out=dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)), flag=bt._empty((bt.B,), "int64"),
-                                                        resid=bt._empty((bt.B,)), passes=bt._empty((bt.B,), "int64")))
+            pol = bt.polish_device(store=True, select=select,
+                                   out=dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
+                                            resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_()))
             layer.last_polish = {k: pol[k] for k in ("flag", "res", "resid", "passes")}
-        fctx.layer, fctx.epoch = layer, bt.epoch
+        fctx.layer, fctx.epoch, fctx.select = layer, bt.epoch, select
         fctx.mark_non_differentiable(out["status_val"])
         return out["x"], out["y"], out["status_val"]
 
@@ -53,12 +68,18 @@ class _QPFunction(torch.autograd.Function):
         need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
         want = tuple(k for k, v in need.items() if v) + ("flag", "resid", "passes")
         gx = bt._empty((bt.B, bt.n)).zero_() if gx is None else gx.contiguous()
-        out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), want=want)
+        select = getattr(fctx, "select", None)
+        if select is None:
+            out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), want=want)
+        else:   # rows of members that are not selected are not written: zero gradients
+            shapes = dict(dq=(bt.B, bt.n), dbmin=(bt.B, bt.m), dbmax=(bt.B, bt.m), dQx=(bt.B, bt.nnzQ), dAx=(bt.B, bt.nnzA), flag=(bt.B,), resid=(bt.B,), passes=(bt.B,))
+            zeros = {k: bt._empty(shapes[k], "int64" if k in ("flag", "passes") else "float64").zero_() for k in want}
+            out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=zeros, select=select)
         layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
-        return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx"))
+        return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx")) + (None,)
 
     @staticmethod
-    def jvp(fctx, _layer, tq, tbmin, tbmax, tQx, tAx):
+    def jvp(fctx, _layer, tq, tbmin, tbmax, tQx, tAx, _tselect=None):
         """forward-mode AD (torch.autograd.forward_ad): the tangent of the solved batch along the inputs' tangents (QpalmBatch.tangent_device)"""
         layer = fctx.layer
         bt = layer.batch
@@ -68,7 +89,13 @@ class _QPFunction(torch.autograd.Function):
         d = [con(t) for t in (tq, tbmin, tbmax, tQx, tAx)]
         if all(t is None for t in d):
             d[0] = bt._empty((bt.B, bt.n)).zero_()
-        out = bt.tangent_device(*d, want=("dx", "dy", "flag", "resid", "passes"))
+        select = getattr(fctx, "select", None)
+        if select is None:
+            out = bt.tangent_device(*d, want=("dx", "dy", "flag", "resid", "passes"))
+        else:   # rows of members that are not selected are not written: zero tangents
+            zeros = dict(dx=bt._empty((bt.B, bt.n)).zero_(), dy=bt._empty((bt.B, bt.m)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
+                         resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_())
+            out = bt.tangent_device(*d, out=zeros, select=select)
         layer.last_tangent = {k: out[k] for k in ("flag", "resid", "passes")}
         return out["dx"], out["dy"], None
 
@@ -82,5 +109,5 @@ class QPLayer(torch.nn.Module):
         self.batch, self.warm, self.last_adjoint, self.last_tangent = batch, warm, None, None
         self.polish, self.last_polish = bool(polish), None
 
-    def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None):
-        return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax)
+    def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None, select=None):
+        return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax, select)
