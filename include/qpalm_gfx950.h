@@ -296,7 +296,8 @@ int  qpg_batch_step_device(qpg_batch *bt, const QPGDeviceStep *io);
  *   entries, which the engine ignores, and the padding up to nnzQ_max / nnzA_max get 0) -- the layout qpg_batch_update_Q_A takes.
  * active_in = NULL: J by the engine's own test on the stored solution in scaled space (A x + y / sigma <= bmin: lower, >= bmax: upper; a row with
  * bmin = bmax always, as lower); else -1 = lower, +1 = upper, 0 = inactive.  flag: 0 done; 1 the pass cap (200) was reached or the solve gave a
- * non-finite value; 2 the member's status is not SOLVED / DUAL_TERMINATED.  With flag 1 or 2 every output of the member is zero.  resid = the last
+ * non-finite value (qpg_batch_set_sens_penalty: a penalty floor for the preconditioner, which takes the cap away after loose solves); 2 the member's
+ * status is not SOLVED / DUAL_TERMINATED.  With flag 1 or 2 every output of the member is zero.  resid = the last
  * ||r||inf / (||K||inf ||z||inf + ||rhs||inf) in the engine's scaling (-1: non-finite), passes = corrections applied.  Entries beyond a sized member's
  * own n / m are zero.  Synchronous, like the calls above; all arrays in device memory; inputs are only read.  The call may overwrite the factor slots
  * and scratch vectors a finished solve leaves (the next solve rebuilds them); the iterates, stored solutions, penalties, statuses and counters stay.
@@ -323,7 +324,7 @@ int  qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io);
  * dQx / dAx are read in the layout qpg_batch_update_Q_A takes and the adjoint writes: entry k belongs to the k-th entry the caller passed to
  * qpg_batch_set_problem*; a stored lower entry of Q stands for both symmetric positions, upper entries and the padding up to nnzQ_max / nnzA_max are
  * ignored.  On inactive rows dbmin, dbmax and (dA x)_i are not read.  A NULL direction array is a zero one (the same bits as an array of zeros).
- * K is symmetric, so this is the adjoint's solve on another right-hand side: the same fresh factor, refinement, stopping rule, pass cap (200), flag /
+ * K is symmetric, so this is the adjoint's solve on another right-hand side: the same fresh factor (and penalty floor), refinement, stopping rule, pass cap (200), flag /
  * resid / passes, and <gx, dx> + <gy, dy> = <adjoint outputs of (gx, gy), direction> up to the rounding of the two solves.  With flag 1 or 2 dx and
  * dy of the member are zero.  Entries beyond a sized member's own n / m are ignored on input and zero on output.  Synchronous; all arrays in device
  * memory; inputs are only read; one deterministic launch (no floating-point atomics: two calls on the same state return the same bits).  The call
@@ -347,7 +348,7 @@ int  qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io);
  *   K [dx; dy_J] = [-(q + Q x + A_J' y_J); b_J - A_J x],  b_i = bmin_i on a lower-active row, bmax_i on an upper-active one    (y masked by J),
  *   candidate x^ = x + dx,  y^_i = y_i + dy_i on J and 0 elsewhere; then, on a row of J with bmin < bmax, a multiplier on the wrong side of its bound
  *   (y^_i > 0 on a lower-active row, y^_i < 0 on an upper-active one) is set to zero.
- * The solve is the adjoint's: the same fresh factor, refinement from zero, stopping rule, pass cap (200), resid and passes.  The verdict is taken in
+ * The solve is the adjoint's: the same fresh factor (and penalty floor, qpg_batch_set_sens_penalty), refinement from zero, stopping rule, pass cap (200), resid and passes.  The verdict is taken in
  * unscaled space with the measures of the solver's own termination test: pri(x) = max_i max(bmin_i - (A x)_i, (A x)_i - bmax_i, 0),
  * dua(x, y) = ||Q x + q + A' y||inf, eps_pri = eps_abs + eps_rel max(||A x^||inf, ||clip(A x^, bmin, bmax)||inf), eps_dua = eps_abs + eps_rel
  * max(||Q x^||inf, ||q||inf, ||A' y^||inf) with the batch's current settings; the clipped candidate is accepted iff
@@ -375,6 +376,17 @@ typedef struct {
   qpg_int         *passes;        /* out [B] */
 } QPGDevicePolish;
 int  qpg_batch_polish_device(qpg_batch *bt, const QPGDevicePolish *io);
+/* The penalty floor of the three calls above and of their subset forms.  Their refinement is preconditioned with the factor of
+ * Q + I / gamma + A_J' Sigma_J A_J and contracts by about 1 / (1 + sigma lambda) per pass, so the penalties a loose solve stops with make it slow
+ * (the pass cap, flag 1).  With a floor s > 0 the preconditioner -- the fresh factor and the two places of a pass that multiply by Sigma -- uses
+ * sigma'_i = max(sigma_i, s) on the rows of J.  The system solved, its residual, the stopping rule, the pass cap, resid, passes and the flags are the
+ * same, so a converged member is as accurate as before; the rule for J keeps the solve's own sigma; the member's penalties and everything else of its
+ * state stay bit for bit (solve -> call -> step is solve -> step with any floor).  A row with sigma_i >= s enters as before: s = 0 (the default), or
+ * any s below every penalty, gives the bits of a batch that never set one.  Per batch; allowed before and after qpg_batch_setup; kept across
+ * qpg_batch_setup, the updates, the settings and the solves; applies to every later call.  Stored without effect on batches for which the three calls
+ * are refused.  QPG_ERR_INVALID (value unchanged) for a NULL batch, a negative value, a NaN or an infinity. */
+int  qpg_batch_set_sens_penalty(qpg_batch *bt, qpg_float sigma_floor);
+int  qpg_batch_get_sens_penalty(qpg_batch *bt, qpg_float *out);
 /* ---- the four calls above on a SUBSET of the members.  d_select: [B] qpg_int in device memory, 1 = the member takes part,
  * 0 = it does not; NULL = every member, and the call is its counterpart above.  n_selected (host, may be NULL): how many took part.
  * A member that is not selected is untouched: nothing is read from its rows of the input arrays (a bmin > bmax there is no error), nothing is written

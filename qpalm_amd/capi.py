@@ -140,6 +140,9 @@ def load(path=None):
     if hasattr(L, "qpg_batch_step_subset_device"):   # (absent from older builds of the library that tools/evidence/subset_step_timing.py compares with)
         for f, io in (("step", DeviceStep), ("adjoint", DeviceAdjoint), ("tangent", DeviceTangent), ("polish", DevicePolish)):
             getattr(L, "qpg_batch_%s_subset_device" % f).argtypes = [C.c_void_p, C.POINTER(io), C.c_void_p, pi]
+    if hasattr(L, "qpg_batch_set_sens_penalty"):   # (absent from older builds of the library that tools/evidence/polish_timing.py compares with)
+        L.qpg_batch_set_sens_penalty.argtypes = [C.c_void_p, c_float]
+        L.qpg_batch_get_sens_penalty.argtypes = [C.c_void_p, pf]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -194,6 +197,7 @@ SYMBOLS = [
     "qpg_batch_get_status_device", "qpg_batch_step_device", "qpg_batch_get_sparse_factor", "qpg_batch_adjoint_device",
     "qpg_batch_tangent_device", "qpg_batch_polish_device",
     "qpg_batch_step_subset_device", "qpg_batch_adjoint_subset_device", "qpg_batch_tangent_subset_device", "qpg_batch_polish_subset_device",
+    "qpg_batch_set_sens_penalty", "qpg_batch_get_sens_penalty",
 ]
 
 

@@ -14,6 +14,13 @@
  * SpMVs for the residual, one more and a triangular solve for du, one more for dw.  It stops with the correction of the first residual that has
  * ||r||inf <= 4 eps (||K~||inf ||z||inf + ||rhs||inf) (a backward-stable solve), or at the pass cap (flag 1).
  *
+ * The penalty floor (qpg_adjoint_args.sens_floor, qpg_batch_set_sens_penalty): a pass contracts by about 1 / (1 + sigma lambda), so the
+ * penalties a loose solve stops with make the refinement slow, and nothing in the linear solve needs them.  With a floor s > 0 the preconditioner uses
+ * sigma'_i = max(sigma_i, s) on J -- in F (form_schur / sp_factor with BOOST: a row below the floor takes the factor s / sigma_i once, where its entry of
+ * the column is read; At_sqrt_sigma itself, the reference's running product, is only read) and in the two places of a pass that multiply by Sigma.  K~,
+ * the residual, the stopping rule and the outputs do not see it; the rule for J keeps the solve's sigma_inv (it is a statement about the stored solution).
+ * A row with sigma_i >= s contributes the same terms in the same order: s = 0, or any s below every penalty, gives the same bits as no floor.
+ *
  * The tangent (qpg_batch_tangent_device) is the same solve, K being symmetric, on the right-hand side of a direction of the data:
  *   r1 = -(dq + dQ x + dA' y),  r2_i = db_i - (dA x)_i on J,  K [dx; dy_J] = [r1; r2]  -- a mode of the same kernel (qpg_adjoint_args.tangent).
  * sens_setup (step 1: active set, scaled solution, ||K~||inf, the fresh factor) and sens_refine (step 2: the refinement on a given right-hand side and
@@ -59,7 +66,8 @@ QPD SensVecs sens_vecs(const QpArrays &a) {
  * in keep), z = [u; w] = 0, and F = Q~ (+ I / gamma) + A~_J' Sigma_J A~_J factorised afresh: the slot may hold another member's factor, or this member's
  * for another set.  Returns ||K~||inf (largest absolute row sum). ---- */
 template <int RPT>
-QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, const int64_t *active_in, int b, int slot, IterShared &I, char *lds) {
+QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, const int64_t *active_in, int b, int slot, IterShared &I, char *lds,
+                      const double sfloor) {
   constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
   const qpg_settings &st = *V.settings;
   const int n = a.n, m = a.m, tid = threadIdx.x;
@@ -104,9 +112,9 @@ QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, c
   block_reduce<1, 0>(I.S, vm, vs);
   if constexpr (SPARSE) {
     const SpArrays SP = sp_arrays(V, b, slot, Dg, lds);
-    if (QP_CALL_BLOCK()) sp_factor(V, b, n, SP, true, prox != 0, gam);
+    if (QP_CALL_BLOCK()) sp_factor<false, true>(V, b, n, SP, true, prox != 0, gam, 0, 0, -1, 0, 0, sfloor);
   } else {
-    form_schur(V, b, n, L, false, true, prox != 0, gam, I.S, lds);
+    form_schur<true>(V, b, n, L, false, true, prox != 0, gam, I.S, lds, 0, 1, sfloor);
     dev_factor<RPT>(V, n, L, Dg, lds, I.s.ticks_dbg);
   }
   return vm[0];
@@ -116,7 +124,7 @@ QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, c
  * (u = D u~, w = E w~ / c; zeros when flagged) and the flags of the active set back where the next solve expects them ---- */
 template <int RPT>
 QPN void sens_refine(const qpg_view &V, const QpArrays &a, const SensVecs &v, int b, int slot, IterShared &I, char *lds, double normK, int max_pass,
-                     int &flag, int &passes, double &ratio) {
+                     const double sfloor, int &flag, int &passes, double &ratio) {
   constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
   const int n = a.n, m = a.m, tid = threadIdx.x;
   const int scal = I.s.has_scaling;
@@ -156,14 +164,14 @@ QPN void sens_refine(const qpg_view &V, const QpArrays &a, const SensVecs &v, in
     /* the correction this residual gives is applied in either case: the iteration converges linearly, so the iterate whose residual first meets the
      * bound sits AT the bound, and its correction is what takes the error down to the rounding level of the solve (`passes` counts it) */
     passes = pass + 1;
-    for (int i = tid; i < m; i += QP_T) t[i] = sgn[i] ? a.sigma()[i] * r2[i] : 0.0;
+    for (int i = tid; i < m; i += QP_T) t[i] = sgn[i] ? qmax(a.sigma()[i], sfloor) * r2[i] : 0.0;
     __syncthreads();
     spmv_rows<16>(n, a.Ap(), a.Ai(), a.Ax(), (const double *)t, [&](int r, double s) { xs[r] = r1[r] + s; });
     __syncthreads();
     if constexpr (SPARSE) { if (QP_CALL_BLOCK()) sp_solve(n, sp_arrays(V, b, slot, Dg, lds), xs); }
     else { if (QP_CALL_BLOCK()) dense_solve(L, Dg, n, V.ld, xs, lds, V.lds_bytes); }
     __syncthreads();
-    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { if (sgn[r]) w[r] = w[r] + a.sigma()[r] * (s - r2[r]); });
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { if (sgn[r]) w[r] = w[r] + qmax(a.sigma()[r], sfloor) * (s - r2[r]); });
     for (int j = tid; j < n; j += QP_T) u[j] = u[j] + xs[j];
     if (conv) break;
   }
@@ -375,6 +383,7 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
   const int n = a.n, m = a.m, tid = threadIdx.x;
   const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
   const int tangent = QP_UNIFORM(io.tangent), polish = QP_UNIFORM(io.polish);
+  const double sfloor = io.sens_floor; /* the preconditioner's penalties: max(sigma_i, sfloor) on J (0: the solve's own) */
   __syncthreads();
   if (tid == 0) I.s = V.sc[b]; /* a copy: the factorisation's timers land in it and go nowhere */
   __syncthreads();
@@ -386,11 +395,11 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
   double *u = v.u, *w = v.w;
   int *sgn = v.sgn;
   if (flag == 0) {
-    const double normK = sens_setup<RPT>(V, a, v, io.active_in, b, slot, I, lds);
+    const double normK = sens_setup<RPT>(V, a, v, io.active_in, b, slot, I, lds, sfloor);
     if (polish) pol_rhs(V, a, v, I, pri_old, dua_old);
     else if (tangent) tan_rhs(V, a, v, io, b, I);
     else adj_rhs(V, a, v, io, b, I);
-    sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, flag, passes, ratio);
+    sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, sfloor, flag, passes, ratio);
   }
   if (polish) pol_finish(V, a, v, io, b, I, flag, pri_old, dua_old); /* (x, y, res and the store; the outputs below that a polish has are written there) */
   /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros ---- */

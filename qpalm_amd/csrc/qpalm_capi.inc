@@ -211,6 +211,7 @@ struct qpg_batch {
    * moment, in one transfer (raw_need_host / raw_need_device). */
   std::vector<double> raw_h;
   void *raw_d = nullptr; int raw_cur = 0;
+  double sens_floor = 0.0; /* qpg_batch_set_sens_penalty: the penalty floor of the sensitivity solves' preconditioner (0: the solve's own penalties) */
   double *raw_q() { return raw_h.data(); }
   double *raw_bmin() { return raw_h.data() + (size_t)B * n; }
   double *raw_bmax() { return raw_h.data() + (size_t)B * n + (size_t)B * m; }
@@ -2027,6 +2028,19 @@ extern "C" int qpg_batch_step_subset_device(qpg_batch *bt, const QPGDeviceStep *
  * off the work queue.  Pass cap of the refinement: 200 (a pass contracts the error by about 1 / (1 + sigma lambda), lambda the eigenvalues of
  * A_J Q^-1 A_J': sixteen digits in a handful of passes at the penalties a finished solve holds, and a member that needs more than 200 is flagged). */
 #define QPG_ADJOINT_MAX_PASS 200
+/* The penalty floor of the three sensitivity calls (include/qpalm_gfx950.h; DESIGN.md section 16): a number of the batch, kept by everything but
+ * qpg_batch_destroy; sens_launch hands it to the kernel. */
+extern "C" int qpg_batch_set_sens_penalty(qpg_batch *bt, qpg_float sigma_floor) {
+  if (!bt) return fail(QPG_ERR_INVALID, "qpg_batch_set_sens_penalty: NULL");
+  if (!(sigma_floor >= 0.0 && sigma_floor <= 1.7976931348623157e308)) return fail(QPG_ERR_INVALID, "qpg_batch_set_sens_penalty: the floor must be finite and >= 0");
+  bt->sens_floor = sigma_floor;
+  return QPG_OK;
+}
+extern "C" int qpg_batch_get_sens_penalty(qpg_batch *bt, qpg_float *out) {
+  if (!bt || !out) return fail(QPG_ERR_INVALID, "qpg_batch_get_sens_penalty: NULL");
+  *out = bt->sens_floor;
+  return QPG_OK;
+}
 /* what the adjoint and the tangent refuse alike: modes without the Schur factor, a solve in progress (the scalars come over for it: one transfer of
  * B qpg_scalars per call, DESIGN.md section 13), a bad active_in */
 static int sens_refusals(qpg_batch *bt, const std::string &fn, const qpg_int *active_in) {
@@ -2052,7 +2066,7 @@ static int sens_refusals(qpg_batch *bt, const std::string &fn, const qpg_int *ac
 }
 /* the launch of k_adjoint (either mode); maps: the call reads or writes per-entry arrays in the caller's order */
 static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps, const Subset &sub) {
-  ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS;
+  ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS; ar.sens_floor = bt->sens_floor;
   if (maps) {
     int32_t *mapA_d, *mapQ_d, *same_d;
     const int rcm = value_maps_device(bt, &mapA_d, &mapQ_d, &same_d);

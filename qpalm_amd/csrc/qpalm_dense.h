@@ -91,7 +91,11 @@ QPD double qp_rcp(double x) {
  * number of rounds (measured on mpc-160, n = 160: 0.25 ms per assembly with one wavefront per column, 40 rounds).
  * Same order of additions per entry as form_schur (active rows t ascending).
  * ------------------------------------------------------------------------------------------- */
-QPN void form_schur_narrow(const qpg_view &V, int b, const int n, double *Lslot, bool with_AtSA, bool proximal, double gamma, char *lds) {
+/* BOOST (the sensitivity solves' penalty floor, qpalm_adjoint.h): a row t with sigma_t < sfloor enters as sfloor a_t a_t' instead of sigma_t a_t a_t' -- its
+ * entry of column j takes the factor sfloor / sigma_t once, where it is read; every other row contributes the same terms in the same order. */
+QPD double schur_boost(const double v, const double sigma, const double sfloor) { return (sigma < sfloor) ? v * (sfloor / sigma) : v; }
+template <bool BOOST = false>
+QPN void form_schur_narrow(const qpg_view &V, int b, const int n, double *Lslot, bool with_AtSA, bool proximal, double gamma, char *lds, const double sfloor = 0.0) {
   const int ld = V.ld;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, grp = lane >> 4, gl = lane & 15;
   const int *Ap = V.Ap + (size_t)b * (V.n + 1), *Ai = V.Ai + (size_t)b * V.nnzA;
@@ -120,7 +124,10 @@ QPN void form_schur_narrow(const qpg_view &V, int b, const int n, double *Lslot,
         const int act_l = valid ? active[t_l] : 0;
         int k0_l = 0, cnt_l = 0;
         double vj_l = 0.0;
-        if (act_l) { k0_l = Atp[t_l]; cnt_l = Atp[t_l + 1] - k0_l; vj_l = Atss[Ainv[pidx]]; }
+        if (act_l) {
+          k0_l = Atp[t_l]; cnt_l = Atp[t_l + 1] - k0_l; vj_l = Atss[Ainv[pidx]];
+          if constexpr (BOOST) vj_l = schur_boost(vj_l, V.sigma[(size_t)b * V.m + t_l], sfloor);
+        }
         unsigned gmask = (unsigned)((__ballot(act_l) >> (16 * grp)) & 0xffffull); /* this column's active rows, ascending */
         while (__ballot(gmask != 0)) {
           /* two active rows per step (their entries of F are fetched together), added in ascending order */
@@ -173,9 +180,10 @@ QPN void form_schur_narrow(const qpg_view &V, int b, const int n, double *Lslot,
  * GERSH = true: no Q, full columns, returns max_j (C_jj + sum_{i!=j} |C_ij|)  (nonconvex.c:185-210).
  * (GERSH is a run-time flag so that the kernel holds ONE copy of this loop nest.)
  * ------------------------------------------------------------------------------------------- */
+template <bool BOOST = false> /* (BOOST, sfloor: see schur_boost) */
 QPN double form_schur(const qpg_view &V, int b, const int n, double *Lslot, const bool GERSH, bool with_AtSA, bool proximal, double gamma,
-                      QpShared &S, char *lds, const int wg = 0, const int nwg = 1) { /* (wg, nwg): this workgroup's share of the columns (k_co_form) */
-  if (!GERSH && V.narrow_rows && nwg == 1) { form_schur_narrow(V, b, n, Lslot, with_AtSA, proximal, gamma, lds); return 0.0; }
+                      QpShared &S, char *lds, const int wg = 0, const int nwg = 1, const double sfloor = 0.0) { /* (wg, nwg): this workgroup's share of the columns (k_co_form) */
+  if (!GERSH && V.narrow_rows && nwg == 1) { form_schur_narrow<BOOST>(V, b, n, Lslot, with_AtSA, proximal, gamma, lds, sfloor); return 0.0; }
   const int ld = V.ld; /* n = this QP's dimension; the per-QP strides below are the batch's V.n / V.m */
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int *Ap = V.Ap + (size_t)b * (V.n + 1), *Ai = V.Ai + (size_t)b * V.nnzA;
@@ -210,7 +218,10 @@ QPN double form_schur(const qpg_view &V, int b, const int n, double *Lslot, cons
           const int act_l = valid ? active[t_l] : 0;
           int k0_l = 0, cnt_l = 0;
           double vj_l = 0.0;
-          if (act_l) { k0_l = Atp[t_l]; cnt_l = Atp[t_l + 1] - k0_l; vj_l = Atss[Ainv[pidx]]; }
+          if (act_l) {
+            k0_l = Atp[t_l]; cnt_l = Atp[t_l + 1] - k0_l; vj_l = Atss[Ainv[pidx]];
+            if constexpr (BOOST) vj_l = schur_boost(vj_l, V.sigma[(size_t)b * V.m + t_l], sfloor);
+          }
           unsigned long long mask = __ballot(act_l);
           while (mask) {
             int sl[4], cn[4], kk0[4], ig[4];

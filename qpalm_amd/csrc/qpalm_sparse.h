@@ -85,8 +85,9 @@ QPD bool sp_level_needs_barrier(const SpArrays &S, int lev) {
  * KKT = true (qpalm_sparse_kkt.h; with_AtSA = false): K = [[Q + I / gamma, A_a'], [A_a, -Sigma_a^-1]] of n = nv + m rows instead -- a variable's column
  * (perm[j] < nv) takes Q, 1 / gamma and A's entries toward the constraints with kkt_state 1; such a constraint's column (non-empty: a constraint
  * with an entry) its row of A and -1 / sigma; any other constraint's column a unit diagonal.  The updates and the pivots are the same code. */
-template <bool KKT = false>
-QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma, int nv = 0, int lev0 = 0, int lev1 = -1, int g0 = 0, int gtot = 0) {
+template <bool KKT = false, bool BOOST = false> /* (BOOST, sfloor: the sensitivity solves' penalty floor, see schur_boost in qpalm_dense.h) */
+QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, bool with_AtSA, bool proximal, double gamma, int nv = 0, int lev0 = 0, int lev1 = -1, int g0 = 0, int gtot = 0,
+                    const double sfloor = 0.0) {
   /* a column per GROUP of lanes: the columns of a sparse factor are short (a band: half a dozen entries), so a wavefront takes gpw = 1, 2,
    * 4 or 8 columns of the level at a time (8 lanes each at 8) and a 512-thread workgroup up to 64 -- every step of a column is a chain of
    * dependent HBM round trips, the groups' chains overlap.  Loops run to the wavefront's longest trip count with the other groups
@@ -101,6 +102,11 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
   const double *Qfx = V.Qfx + (size_t)b * V.nnzQf;
   const int *active = V.active + (size_t)b * V.m;
   const int *kstate = V.kkt_state + (size_t)b * V.m; /* (KKT) */
+  /* row t's entry of column j as the assembly takes it (the other factor, the entries of the row, stays Atss) */
+  auto row_entry = [&](const int t, const double v) QP_ALWAYS_INLINE {
+    if constexpr (BOOST) return schur_boost(v, V.sigma[(size_t)b * V.m + t], sfloor);
+    else return v;
+  };
   const double *Ax = V.Ax + (size_t)b * V.nnzA, *Atx = V.Atx + (size_t)b * V.nnzA, *sigma_inv = V.sigma_inv + (size_t)b * V.m;
 #if QP_SP_LOCAL
   const SpArrays S = S_; /* (a real function: the fields of S_ would be re-read from the caller's frame after every store) */
@@ -181,7 +187,7 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
         if (r0 + gl < r1) { f_k = Rk[r0 + gl]; f_tpos = Rpos[r0 + gl]; }
         int f_tq0 = 0, f_tq1 = 0, f_tk1 = 0;
         double f_tv = 0.0, f_tl = 0.0, f_td = 0.0;
-        if (f_t >= 0) { const int act = active[f_t]; const double v = Atss[f_ainv]; const int q0 = Atp[f_t], q1 = Atp[f_t + 1]; if (act) { f_tv = v; f_tq0 = q0; f_tq1 = q1; } }
+        if (f_t >= 0) { const int act = active[f_t]; const double v = Atss[f_ainv]; const int q0 = Atp[f_t], q1 = Atp[f_t + 1]; if (act) { f_tv = row_entry(f_t, v); f_tq0 = q0; f_tq1 = q1; } }
         if (f_k >= 0) { f_tl = Lx[f_tpos]; f_td = Dg[f_k]; f_tk1 = Lp[f_k + 1]; }
         const int np = wave_imax(p1 - p0), nr = wave_imax(r1 - r0);
         /* a batch of QP_SPB rows of A: their entries, one per lane, requested together (load), applied in order (apply) */
@@ -270,7 +276,7 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
             tq0 = 0; tq1 = 0; tv = 0.0;
             if (pm < p1) {
               const int t = Ai[pm];
-              if (active[t]) { tv = Atss[Ainv[pm]]; tq0 = Atp[t]; tq1 = Atp[t + 1]; }
+              if (active[t]) { tv = row_entry(t, Atss[Ainv[pm]]); tq0 = Atp[t]; tq1 = Atp[t + 1]; }
             }
           }
           const int cnt = (np - pb < spg) ? (np - pb) : spg;
@@ -323,7 +329,7 @@ QPNI void sp_factor(const qpg_view &V, int b, const int n, const SpArrays &S_, b
           double tv = 0.0;
           if (pm < p1) {
             const int t = Ai[pm];
-            if (active[t]) { tv = Atss[Ainv[pm]]; tq0 = Atp[t]; tq1 = Atp[t + 1]; }
+            if (active[t]) { tv = row_entry(t, Atss[Ainv[pm]]); tq0 = Atp[t]; tq1 = Atp[t + 1]; }
           }
           const int cnt = (np - pb < spg) ? (np - pb) : spg;
           for (int sidx = 0; sidx < cnt; sidx++) {

@@ -182,6 +182,9 @@ typedef struct {
   /* list != NULL: the call covers a subset (qpg_batch_*_subset_device): the queue hands out list[0], list[1], ... and a workgroup stops at the first
    * entry >= B (qpg_view.order as k_select leaves it); members that are not listed are neither read nor written */
   const int32_t *list;
+  /* the penalty floor of the refinement's preconditioner (qpg_batch_set_sens_penalty): sigma'_i = max(sigma_i, sens_floor) on the rows of J; 0 = the
+   * solve's own penalties */
+  double sens_floor;
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

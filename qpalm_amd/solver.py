@@ -431,6 +431,19 @@ class QpalmBatch:
             out["n_selected"] = cnt
         return out
 
+    @property
+    def sens_penalty(self):
+        """The penalty floor of adjoint_device, tangent_device and polish_device (qpg_batch_set_sens_penalty): the preconditioner of
+        their refinement uses max(sigma_i, floor) on the active rows, which takes the pass cap away after a loose solve.  0 (the default): the solve's
+        own penalties.  A setting of the linear solve alone: the batch's state and `epoch` stay."""
+        v = C.c_double(0.0)
+        self._check(self.L.qpg_batch_get_sens_penalty(self.h, C.byref(v)))
+        return float(v.value)
+
+    @sens_penalty.setter
+    def sens_penalty(self, floor):
+        self._check(self.L.qpg_batch_set_sens_penalty(self.h, float(floor)))
+
     POLISH_OUT = ("x", "y", "res", "active", "flag", "resid", "passes")
 
     def polish_device(self, active_in=None, store=False, want=POLISH_OUT, out=None, select=None):

@@ -102,10 +102,14 @@ class _QPFunction(torch.autograd.Function):
 
 class QPLayer(torch.nn.Module):
     """x*(q, bmin, bmax[, Qx, Ax]) of a set-up QpalmBatch as a torch module.  warm: the warm start of every forward step, as step_device takes it
-    (None = cold, "last" = every member's previous solution).  polish: polish every forward solve and store the result (see above)."""
+    (None = cold, "last" = every member's previous solution).  polish: polish every forward solve and store the result (see above).  sens_penalty: a
+    number sets the batch's penalty floor for the adjoint, tangent and polish solves (QpalmBatch.sens_penalty); None leaves the
+    batch's value alone."""
 
-    def __init__(self, batch, warm=None, polish=False):
+    def __init__(self, batch, warm=None, polish=False, sens_penalty=None):
         super().__init__()
+        if sens_penalty is not None:
+            batch.sens_penalty = sens_penalty
         self.batch, self.warm, self.last_adjoint, self.last_tangent = batch, warm, None, None
         self.polish, self.last_polish = bool(polish), None
 

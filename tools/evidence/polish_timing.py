@@ -12,12 +12,15 @@ the device); the first four in turn, --runs times:
             flag, the medians of pri / dua before and after;
   trade     this build, once: the same batch cold, "solve to 1e-3, then polish with store" against "solve to 1e-9": wall ms of each part and the
             residuals of the stored solutions at the end, over every member (as a further polish call reports them: pri_old / dua_old of whatever is
-            stored -- the candidate where it was accepted, the solve's solution where not).
+            stored -- the candidate where it was accepted, the solve's solution where not).  With --sens-penalty the first arm runs twice: with the
+            solve's own penalties, and with the floor (QpalmBatch.sens_penalty).
+
+--sens-penalty also applies to this build's `adjoint` and `polish` steps (never to `parent`: an older build has no such call).
 
 Per figure: wall ms per call (host clock around a call that ends in a device synchronise), median and minimum of --calls calls after two untimed ones.
 No ratio is judged here: read the figures side by side, and the spread between the runs.
 
-  python tools/evidence/polish_timing.py [--lib PARENT_BUILD.so] [--B 8192] [--calls 10] [--runs 2] [--limit 300]
+  python tools/evidence/polish_timing.py [--lib PARENT_BUILD.so] [--B 8192] [--calls 10] [--runs 2] [--limit 300] [--sens-penalty FLOOR] [--steps forward,adjoint,...]
 
 One JSON line per step."""
 import argparse
@@ -88,12 +91,14 @@ def child(args):
                                                flag=((bt.B,), "int64"), resid=((bt.B,),), passes=((bt.B,), "int64")).items()}
     if args.child == "trade":
         # both arms start cold on the same batch (warm=None: no warm start); the settings change between them
-        for arm, e in (("solve_1e-3_then_polish", 1e-3), ("solve_1e-9", 1e-9)):
+        arms = [("solve_1e-3_then_polish", 1e-3, 0.0)] + ([("solve_1e-3_then_polish_floor", 1e-3, args.sens_penalty)] if args.sens_penalty > 0 else [])
+        for arm, e, floor in arms + [("solve_1e-9", 1e-9, 0.0)]:
+            bt.sens_penalty = floor
             bt.update_settings(ctx.default_settings(eps_abs=e, eps_rel=e, verbose=0))
             bt.step_device(warm=None, out=out)                                     # untimed: the first launch of this shape
             ms_solve = [once(lambda: bt.step_device(warm=None, out=out)) for _ in range(args.calls)]
             solved = int((out["status_val"] == 1).sum().item())
-            d = dict(ms_solve_median=statistics.median(ms_solve), ms_solve_min=min(ms_solve), solved=solved)
+            d = dict(ms_solve_median=statistics.median(ms_solve), ms_solve_min=min(ms_solve), solved=solved, sens_penalty=floor)
             if e == 1e-3:
                 ms_pol = []
                 for _ in range(args.calls):                                        # every timed polish starts from the 1e-3 solution again
@@ -109,6 +114,9 @@ def child(args):
             res[arm] = d
         print(json.dumps(res), flush=True)
         return
+    if args.child != "parent" and args.sens_penalty > 0:
+        bt.sens_penalty = args.sens_penalty
+        res["sens_penalty"] = args.sens_penalty
     bmin = torch.from_numpy(np.stack([p.bmin for p in probs])).to(dev)
     bmax = torch.from_numpy(np.stack([p.bmax for p in probs])).to(dev)
     noise = torch.from_numpy(0.1 * rng.standard_normal((args.warmup + 2 + args.calls, args.B, NX))).to(dev)
@@ -152,14 +160,17 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--limit", type=int, default=300, help="seconds each GPU step may take")
     ap.add_argument("--rehearse", action="store_true", help="run the steps on the host emulator (a check of this script; use a small --B)")
+    ap.add_argument("--sens-penalty", type=float, default=0.0, help="penalty floor of the sensitivity solves' preconditioner (0: the solve's own penalties)")
+    ap.add_argument("--steps", default="forward,adjoint,parent,polish,trade", help="the steps to run, of those above")
     ap.add_argument("--child", choices=("forward", "adjoint", "parent", "polish", "trade"))
     args = ap.parse_args()
     if args.child:
         return child(args)
     steps = [s for s in ("forward", "adjoint", "parent", "polish") if s != "parent" or args.lib] * args.runs + ["trade"]
+    steps = [s for s in steps if s in args.steps.split(",")]
     for step in steps:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", step, "--B", str(args.B),
-               "--calls", str(args.calls), "--warmup", str(args.warmup)] + (["--lib", os.path.abspath(args.lib)] if args.lib else []) + (["--rehearse"] if args.rehearse else [])
+               "--calls", str(args.calls), "--warmup", str(args.warmup), "--sens-penalty", repr(args.sens_penalty)] + (["--lib", os.path.abspath(args.lib)] if args.lib else []) + (["--rehearse"] if args.rehearse else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(r.stdout)
         sys.stdout.flush()

@@ -10,7 +10,9 @@ Per loop: mean iteration count over the timed steps, wall ms per step (host cloc
 predicted loop's figure includes the tangent call and the two additions), solve-kernel ms per step, and for the predicted loop the tangent's flags.
 The loops take turns in blocks of --steps steps; figures are medians over --blocks blocks.  A report, not a gate.
 
-  python tools/evidence/tangent_predictor.py [--B 8192] [--steps 5] [--blocks 5]
+  python tools/evidence/tangent_predictor.py [--B 8192] [--steps 5] [--blocks 5] [--sens-penalty FLOOR]
+
+--sens-penalty: the penalty floor of the tangent's preconditioner (QpalmBatch.sens_penalty) on the predicted loop's batch.
 
 One JSON line."""
 import argparse
@@ -76,6 +78,7 @@ def main():
     ap.add_argument("--B", type=int, default=8192)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--sens-penalty", type=float, default=0.0)
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs an MI355X: there is no CPU fallback"
@@ -87,6 +90,7 @@ def main():
     probs = mpc_problems(a.B, rng)
     st = ctx.default_settings(eps_abs=1e-6, eps_rel=1e-6, verbose=0)
     loops = {"last": Loop(torch, ctx, probs, st, False), "last_xy": Loop(torch, ctx, probs, st, "xy"), "predicted": Loop(torch, ctx, probs, st, True)}
+    loops["predicted"].bt.sens_penalty = a.sens_penalty
     rows = {k: [] for k in loops}
     for blk in range(a.blocks + 1):                          # block 0: warm-up, not recorded
         noises = [torch.from_numpy(rng.standard_normal((a.B, NX))).to("cuda:0") for _ in range(a.steps)]
@@ -94,7 +98,7 @@ def main():
             r = lp.block(noises, blk > 0)
             if blk > 0:
                 rows[k].append(r)
-    out = dict(tool="tangent_predictor", workload="mpc-160", B=a.B, steps=a.steps, blocks=a.blocks)
+    out = dict(tool="tangent_predictor", workload="mpc-160", B=a.B, steps=a.steps, blocks=a.blocks, sens_penalty=a.sens_penalty)
     for k, lp in loops.items():
         out[k] = dict(mean_iterations=float(np.mean(lp.iters)), wall_ms_per_step=statistics.median(r[0] for r in rows[k]),
                       wall_blocks=[r[0] for r in rows[k]], solve_kernel_ms_per_step=statistics.median(r[1] for r in rows[k]),

@@ -12,7 +12,9 @@ the device), the two builds in turn, --runs times:
 Per figure: wall ms per call (host clock around a call that ends in a device synchronise), median and minimum of --calls calls after two untimed ones.
 No ratio is judged here: read the figures side by side, and the spread between the runs.
 
-  python tools/evidence/tangent_timing.py --lib PARENT_BUILD.so [--B 8192] [--calls 10] [--runs 2] [--limit 300]
+  python tools/evidence/tangent_timing.py --lib PARENT_BUILD.so [--B 8192] [--calls 10] [--runs 2] [--limit 300] [--sens-penalty FLOOR]
+
+--sens-penalty: the penalty floor of the preconditioner (QpalmBatch.sens_penalty) for this build's tangent calls.
 
 One JSON line per step and one at the end."""
 import argparse
@@ -61,7 +63,9 @@ def child(args):
         bmax[:, :NX] = x0
         rc, _ = bt.step_device(bmin, bmax, warm="last", out=out)
         assert rc == 0
-    res = dict(step=args.child, lib=(args.lib if args.child == "adjoint" else "this build"), B=bt.B, n=bt.n, m=bt.m,
+    if args.child == "tangent":
+        bt.sens_penalty = args.sens_penalty
+    res = dict(step=args.child, lib=(args.lib if args.child == "adjoint" else "this build"), B=bt.B, n=bt.n, m=bt.m, sens_penalty=args.sens_penalty if args.child == "tangent" else 0.0,
                solved=int((out["status_val"] == 1).sum().item()))
     rnd = lambda *shape: torch.from_numpy(rng.standard_normal(shape)).to(dev)
     flags = lambda o: dict(flag0=int((o["flag"] == 0).sum().item()), flag1=int((o["flag"] == 1).sum().item()), flag2=int((o["flag"] == 2).sum().item()),
@@ -89,6 +93,7 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--limit", type=int, default=300, help="seconds each GPU step may take")
     ap.add_argument("--lib", default=None, help="the other build, whose adjoint call is timed")
+    ap.add_argument("--sens-penalty", type=float, default=0.0)
     ap.add_argument("--child", choices=("adjoint", "tangent"))
     args = ap.parse_args()
     if args.child:
@@ -97,7 +102,7 @@ def main():
     for _ in range(args.runs):
         for step in (("adjoint", "tangent") if args.lib else ("tangent",)):
             cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", step, "--B", str(args.B),
-                   "--calls", str(args.calls), "--warmup", str(args.warmup)] + (["--lib", args.lib] if args.lib else [])
+                   "--calls", str(args.calls), "--warmup", str(args.warmup), "--sens-penalty", repr(args.sens_penalty)] + (["--lib", args.lib] if args.lib else [])
             r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             sys.stdout.write(r.stdout)
             sys.stdout.flush()
