@@ -407,6 +407,35 @@ int  qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, 
 int  qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected);
 /* The polish of the selected members; with store, accepted candidates of selected members replace their stored solutions. */
 int  qpg_batch_polish_subset_device(qpg_batch *bt, const QPGDevicePolish *io, const qpg_int *d_select, qpg_int *n_selected);
+/* ---- the active set on its own, and the adjoint and the tangent at a RECORDED point.
+ * The active set of the stored solutions by the rule the adjoint applies with active_in = NULL: d_active [B][m] in device memory, -1 lower, +1 upper,
+ * 0 inactive; rows beyond a sized member's own m are 0 and a member whose status is not SOLVED / DUAL_TERMINATED gets all zeros.  Bit for bit the
+ * active_out of qpg_batch_adjoint_device on the same state.  It may overwrite two of the scratch vectors the adjoint may overwrite and nothing else.
+ * The subset form writes the rows of selected members only (d_select, n_selected: as above).  QPG_ERR_INVALID before qpg_batch_setup, while a solve is
+ * in progress and for d_active = NULL; QPG_ERR_UNSUPPORTED for FACTORIZE_KKT batches, coop mode and nonconvex settings. */
+int  qpg_batch_get_active_device(qpg_batch *bt, qpg_int *d_active /* [B][m] */);
+int  qpg_batch_get_active_subset_device(qpg_batch *bt, qpg_int *d_active, const qpg_int *d_select, qpg_int *n_selected);
+/* A recorded point: the solution (x, y) of some earlier solve of this batch and its active set (qpg_batch_get_active_device right after that solve, or
+ * the active_out of a sensitivity call made then).  The system K [u; w] = rhs the adjoint and the tangent solve holds Q, A and the active set; it
+ * holds neither q nor the bounds, and x, y enter only the tangent's right-hand side and the adjoint's dAx / dQx.  So the two calls below are
+ * qpg_batch_adjoint_subset_device / qpg_batch_tangent_subset_device with (x, y) := at->x, at->y and J := at->active wherever those read the stored
+ * solution: the same system, refinement, stopping rule, pass cap, flag 0 / 1, resid, passes; active_out = at->active (signs).  d_select = NULL: every
+ * member.  The members' current statuses are not consulted (flag 2 does not occur): exclude members through d_select.  The preconditioner uses the
+ * members' current penalties and gamma and the penalty floor, as always.  Entries of at->x / at->y beyond a sized member's own n / m are not read; a
+ * member with a non-finite entry within them gets flag 1 and zeros, its neighbours are unaffected.  State: as for the adjoint -- the call neither
+ * reads nor moves the stored solutions, and solve -> call -> step is bit for bit solve -> step.  There is no polish at a point (it needs q and the bounds).
+ * VALIDITY: the values of Q and A (and with them the scaling) must be those of the solve that produced the point -- no qpg_batch_update_Q_A* and no
+ * new setup in between.  q, the bounds, the penalties, warm starts and any number of later solves may differ.  The engine cannot verify this; the
+ * Python layer does (QpalmBatch.matrix_epoch).
+ * QPG_ERR_INVALID: as for the counterpart, and for at = NULL, a NULL field of it, io->active_in != NULL (one source for J) and an entry of
+ * at->active outside {-1, 0, 1}; QPG_ERR_UNSUPPORTED as for the counterpart. */
+typedef struct {
+  const qpg_float *x;       /* [B][n] */
+  const qpg_float *y;       /* [B][m] */
+  const qpg_int   *active;  /* [B][m]: -1 lower, +1 upper, 0 inactive */
+} QPGDevicePoint;
+int  qpg_batch_adjoint_at_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
+int  qpg_batch_tangent_at_device(qpg_batch *bt, const QPGDeviceTangent *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -75,6 +75,11 @@ class DevicePolish(C.Structure):
     _fields_ = [("active_in", C.c_void_p), ("store", c_int)] + [(k, C.c_void_p) for k in ("x", "y", "res", "active_out", "flag", "resid", "passes")]
 
 
+class DevicePoint(C.Structure):
+    """QPGDevicePoint: a recorded point of qpg_batch_adjoint_at_device / qpg_batch_tangent_at_device, all addresses in device memory (all required)"""
+    _fields_ = [(k, C.c_void_p) for k in ("x", "y", "active")]
+
+
 class QpgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("qpalm_gfx950 error %d: %s" % (code, msg))
@@ -143,6 +148,11 @@ def load(path=None):
     if hasattr(L, "qpg_batch_set_sens_penalty"):   # (absent from older builds of the library that tools/evidence/polish_timing.py compares with)
         L.qpg_batch_set_sens_penalty.argtypes = [C.c_void_p, c_float]
         L.qpg_batch_get_sens_penalty.argtypes = [C.c_void_p, pf]
+    if hasattr(L, "qpg_batch_adjoint_at_device"):   # (absent from older builds of the library that tools/evidence/replay_timing.py compares with)
+        L.qpg_batch_get_active_device.argtypes = [C.c_void_p, C.c_void_p]
+        L.qpg_batch_get_active_subset_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, pi]
+        L.qpg_batch_adjoint_at_device.argtypes = [C.c_void_p, C.POINTER(DeviceAdjoint), C.POINTER(DevicePoint), C.c_void_p, pi]
+        L.qpg_batch_tangent_at_device.argtypes = [C.c_void_p, C.POINTER(DeviceTangent), C.POINTER(DevicePoint), C.c_void_p, pi]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -198,6 +208,7 @@ SYMBOLS = [
     "qpg_batch_tangent_device", "qpg_batch_polish_device",
     "qpg_batch_step_subset_device", "qpg_batch_adjoint_subset_device", "qpg_batch_tangent_subset_device", "qpg_batch_polish_subset_device",
     "qpg_batch_set_sens_penalty", "qpg_batch_get_sens_penalty",
+    "qpg_batch_get_active_device", "qpg_batch_get_active_subset_device", "qpg_batch_adjoint_at_device", "qpg_batch_tangent_at_device",
 ]
 
 

@@ -40,6 +40,11 @@
  *   leaving pol_finish          xs = 0, as sens_refine leaves it
  * sol_x / sol_y are read by sens_setup, pol_rhs and pol_finish and written, if at all, by the last loop of pol_finish.
  *
+ * At a recorded point (qpg_batch_adjoint_at_device / qpg_batch_tangent_at_device): K holds Q, A and J and neither q nor the bounds, and
+ * x, y enter only tan_rhs and the dAx / dQx outputs, so a solve from any number of steps ago is differentiated from its x, y and J as long as the values
+ * of Q and A are still its own.  qpg_adjoint_args.at_x / at_y replace sol_x / sol_y wherever dev_adjoint hands a point on, J is active_in, and the
+ * member's status -- that of a later solve -- is not consulted.  k_get_active gives the J of the stored solutions on its own, by sens_setup's rule.
+ *
  * Scratch: vectors a finished solve leaves behind and the next one rebuilds before it reads them (d, temp_n, delta_x, dphi, z, temp_m, delta_y,
  * the line-search scratch, enter / leave) and the workgroup's factor slot.  The active flags form_schur / sp_factor read are saved and put back
  * (update_sigma of a later solve may read them before its first Newton step).  x, y, the stored solution, sigma, gamma, Qx / Ax products and
@@ -62,12 +67,23 @@ QPD SensVecs sens_vecs(const QpArrays &a) {
   return v;
 }
 
+/* The rule for J on a solution: set_active_constraints (newton.c:122-131) at row i, with t = A~ x~ and y the unscaled multipliers; an equality row counts
+ * as lower.  -1 lower, +1 upper, 0 inactive.  One copy for sens_setup and k_get_active: the two give the same bits. */
+QPD int sens_active_row(const QpArrays &a, const double *t, const double *y, int i, int scal, double c) {
+  double yv = y[i];
+  if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
+  const double axys = t[i] + 1 * (yv * a.sigma_inv()[i]);
+  const double lo = a.bmin()[i], hi = a.bmax()[i];
+  return (lo == hi || axys <= lo) ? -1 : ((axys >= hi) ? 1 : 0);
+}
+
 /* ---- step 1 of a sensitivity solve (adjoint and tangent): the scaled solution xs, the active set (sgn; the flags form_schur / sp_factor read are saved
  * in keep), z = [u; w] = 0, and F = Q~ (+ I / gamma) + A~_J' Sigma_J A~_J factorised afresh: the slot may hold another member's factor, or this member's
- * for another set.  Returns ||K~||inf (largest absolute row sum). ---- */
+ * for another set.  px / py: the point (the stored solution, or the caller's of a call "at" a recorded point, for which J is always given).  Returns
+ * ||K~||inf (largest absolute row sum). ---- */
 template <int RPT>
-QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, const int64_t *active_in, int b, int slot, IterShared &I, char *lds,
-                      const double sfloor) {
+QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, const double *px, const double *py, const int64_t *active_in, int b, int slot,
+                      IterShared &I, char *lds, const double sfloor) {
   constexpr bool SPARSE = (RPT == QPG_RPT_SPARSE);
   const qpg_settings &st = *V.settings;
   const int n = a.n, m = a.m, tid = threadIdx.x;
@@ -76,7 +92,7 @@ QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, c
   const int scal = I.s.has_scaling, prox = qp_prox(st, I.s);
   const double c = I.s.sc_c, gam = I.s.gamma;
   for (int j = tid; j < n; j += QP_T) {
-    v.xs[j] = scal ? a.sol_x()[j] * a.Dinv()[j] : a.sol_x()[j];
+    v.xs[j] = scal ? px[j] * a.Dinv()[j] : px[j];
     v.u[j] = 0.0;
   }
   __syncthreads();
@@ -85,13 +101,7 @@ QPN double sens_setup(const qpg_view &V, const QpArrays &a, const SensVecs &v, c
   for (int i = tid; i < m; i += QP_T) {
     int sg;
     if (active_in) { const int64_t av = active_in[om + i]; sg = (av < 0) ? -1 : ((av > 0) ? 1 : 0); }
-    else { /* set_active_constraints (newton.c:122-131) on the stored solution; an equality row counts as lower */
-      double yv = a.sol_y()[i];
-      if (scal) { yv = yv * a.Einv()[i]; yv *= c; }
-      const double axys = v.t[i] + 1 * (yv * a.sigma_inv()[i]);
-      const double lo = a.bmin()[i], hi = a.bmax()[i];
-      sg = (lo == hi || axys <= lo) ? -1 : ((axys >= hi) ? 1 : 0);
-    }
+    else sg = sens_active_row(a, v.t, py, i, scal, c);
     v.sgn[i] = sg; v.keep[i] = v.act[i]; v.act[i] = (sg != 0) ? 1 : 0;
     v.w[i] = 0.0;
   }
@@ -223,10 +233,11 @@ QPN void adj_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const 
 }
 
 /* ---- the tangent's right-hand side: r1 = -(dq + dQ x + dA' y), r2_i = db_i - (dA x)_i on J, formed in unscaled space from the
- * stored solution and the caller's directions, then [c D r1; E r2].  y is the stored y of every row.  dQx / dAx are read where the caller put them
- * (k_update_Q_A's maps): dA' y by the columns of A, dQ x by the rows of the full symmetric pattern (Qfperm: a stored lower entry stands for both
+ * point (x, y: the stored solution, or the caller's recorded one) and the caller's directions, then [c D r1; E r2].  y is that of every row.  dQx / dAx
+ * are read where the caller put them (k_update_Q_A's maps): dA' y by the columns of A, dQ x by the rows of the full symmetric pattern (Qfperm: a stored lower entry stands for both
  * positions; upper entries of the caller are in no map), dA x by the rows of A' (Atperm) -- gathers, eight lanes per column / row. ---- */
-QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, const IterShared &I) {
+QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, const double *x, const double *y, int b,
+                 const IterShared &I) {
   const int n = a.n, m = a.m, scal = I.s.has_scaling;
   const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
   const double c = I.s.sc_c;
@@ -234,7 +245,6 @@ QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const 
   const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr, *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
   const double *dA = io.t_dAx ? io.t_dAx + (size_t)b * io.strideA : nullptr, *dQ = io.t_dQx ? io.t_dQx + (size_t)b * io.strideQ : nullptr;
   const int *Atperm = a.Atperm(), *Qfperm = a.Qfperm();
-  const double *x = a.sol_x(), *y = a.sol_y();
   double *r1 = v.r1;
   auto all = [](int) { return true; };
   for (int j = threadIdx.x; j < n; j += QP_T) r1[j] = io.t_dq ? io.t_dq[on + j] : 0.0;
@@ -387,17 +397,32 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
   __syncthreads();
   if (tid == 0) I.s = V.sc[b]; /* a copy: the factorisation's timers land in it and go nowhere */
   __syncthreads();
+  /* the point: the member's stored solution, or the caller's recorded one (qpg_batch_*_at_device: the status is that of another solve and is not
+   * consulted; J = active_in, which the host requires) */
+  const bool at = (io.at_x != nullptr);
+  const double *px = at ? io.at_x + on : a.sol_x(), *py = at ? io.at_y + om : a.sol_y();
   const int status = QP_UNIFORM(I.s.status);
-  int flag = (status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
+  int flag = (at || status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
   int passes = 0;
   double ratio = 0.0, pri_old = 0.0, dua_old = 0.0;
   const SensVecs v = sens_vecs(a);
   double *u = v.u, *w = v.w;
   int *sgn = v.sgn;
+  if (at) { /* a point that is not finite within the member's own n / m: flag 1 and zeros, nothing is solved; active_out is still the set given */
+    double vs[1] = {0.0};
+    for (int j = tid; j < n; j += QP_T) vs[0] += (double)adj_bad(px[j]);
+    for (int i = tid; i < m; i += QP_T) vs[0] += (double)adj_bad(py[i]);
+    block_reduce<0, 1>(I.S, vs, vs);
+    if (QP_UNIFORM((int)(vs[0] != 0.0))) {
+      flag = 1;
+      for (int i = tid; i < m; i += QP_T) { const int64_t av = io.active_in[om + i]; sgn[i] = (av < 0) ? -1 : ((av > 0) ? 1 : 0); }
+      __syncthreads();
+    }
+  }
   if (flag == 0) {
-    const double normK = sens_setup<RPT>(V, a, v, io.active_in, b, slot, I, lds, sfloor);
+    const double normK = sens_setup<RPT>(V, a, v, px, py, io.active_in, b, slot, I, lds, sfloor);
     if (polish) pol_rhs(V, a, v, I, pri_old, dua_old);
-    else if (tangent) tan_rhs(V, a, v, io, b, I);
+    else if (tangent) tan_rhs(V, a, v, io, px, py, b, I);
     else adj_rhs(V, a, v, io, b, I);
     sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, sfloor, flag, passes, ratio);
   }
@@ -429,10 +454,10 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
       const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1;
       const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr;
       for (int j = tid >> 3; j < n; j += QP_T >> 3) {
-        const double uj = u[j], xj = a.sol_x()[j];
+        const double uj = u[j], xj = px[j];
         for (int k = a.Ap()[j] + (tid & 7); k < a.Ap()[j + 1]; k += 8) {
           const int i = a.Ai()[k];
-          o[sameA ? k : mA[k]] = -(a.sol_y()[i] * uj + w[i] * xj);
+          o[sameA ? k : mA[k]] = -(py[i] * uj + w[i] * xj);
         }
       }
     }
@@ -445,10 +470,10 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
       const int sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
       const int32_t *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
       for (int j = tid >> 3; j < n; j += QP_T >> 3) {
-        const double uj = u[j], xj = a.sol_x()[j];
+        const double uj = u[j], xj = px[j];
         for (int k = a.Qp()[j] + (tid & 7); k < a.Qp()[j + 1]; k += 8) {
           const int i = a.Qi()[k]; /* i >= j: the stored entry stands for both symmetric positions */
-          o[sameQ ? k : mQ[k]] = (i == j) ? -(uj * xj) : -(u[i] * xj + uj * a.sol_x()[i]);
+          o[sameQ ? k : mQ[k]] = (i == j) ? -(uj * xj) : -(u[i] * xj + uj * px[i]);
         }
       }
     }
@@ -471,6 +496,29 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_a
     if (b < V.B && io.list != nullptr) b = QP_UNIFORM(io.list[b]); /* a subset: the listed members, then B (k_select) */
     if (b >= V.B) break;
     dev_adjoint<RPT>(V, io, b, blockIdx.x, I, lds);
+  }
+}
+
+/* qpg_batch_get_active_device: the active set of the stored solutions by the rule of sens_setup (sens_active_row on t = A~ x~), into the caller's [B][m]
+ * array: -1 lower, +1 upper, 0 inactive; rows beyond a member's own m and every row of a member that is not SOLVED / DUAL_TERMINATED are 0.  One
+ * workgroup per listed member (qp_listed).  Scratch: d and ls_delta, as in sens_setup; the active flags are not touched. */
+__global__ __launch_bounds__(QP_T) void k_get_active(qpg_view V, int64_t *out, const int32_t *list) {
+  for (int h = blockIdx.x, b; h < V.B && (b = qp_listed(list, h)) < V.B; h += gridDim.x) {
+    const QpArrays a = qp_arrays(V, b);
+    const int n = a.n, m = a.m, tid = threadIdx.x;
+    const int status = QP_UNIFORM(V.sc[b].status), scal = QP_UNIFORM(V.sc[b].has_scaling);
+    const double c = V.sc[b].sc_c;
+    int64_t *o = out + (size_t)b * V.m;
+    if (status != QPG_SOLVED && status != QPG_DUAL_TERMINATED) {
+      for (int i = tid; i < V.m; i += QP_T) o[i] = 0;
+      continue;
+    }
+    double *xs = a.d(), *t = a.ls_delta();
+    for (int j = tid; j < n; j += QP_T) xs[j] = scal ? a.sol_x()[j] * a.Dinv()[j] : a.sol_x()[j];
+    __syncthreads();
+    spmv_rows<8>(m, a.Atp(), a.Ati(), a.Atx(), (const double *)xs, [&](int r, double s) { t[r] = s; });
+    __syncthreads();
+    for (int i = tid; i < V.m; i += QP_T) o[i] = (i < m) ? sens_active_row(a, t, a.sol_y(), i, scal, c) : 0;
   }
 }
 

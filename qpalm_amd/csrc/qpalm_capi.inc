@@ -2091,38 +2091,79 @@ static int sens_select(qpg_batch *bt, const std::string &fn, const qpg_int *d_se
   if (sub.S == 0) { rc = api_ok(); return 1; }
   return 0;
 }
-extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) { return qpg_batch_adjoint_subset_device(bt, io, nullptr, nullptr); }
-extern "C" int qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const qpg_int *d_select, qpg_int *n_selected) {
-  const std::string fn = d_select ? "qpg_batch_adjoint_subset_device" : "qpg_batch_adjoint_device";
+/* the recorded point of the *_at_device calls (include/qpalm_gfx950.h; DESIGN.md section 17): all three arrays, and the point's set is the only source
+ * for J.  use_at: the call is an "at" form (at == NULL is an error there). */
+static int sens_point(const std::string &fn, bool use_at, const QPGDevicePoint *at, const qpg_int *io_active_in, const qpg_int **active_in) {
+  *active_in = io_active_in;
+  if (!use_at) return QPG_OK;
+  if (!at || !at->x || !at->y || !at->active) return fail(QPG_ERR_INVALID, fn + ": the point needs x, y and active");
+  if (io_active_in) return fail(QPG_ERR_INVALID, fn + ": active_in together with a point (the point's active set is the one used)");
+  *active_in = at->active;
+  return QPG_OK;
+}
+static int adjoint_run(qpg_batch *bt, const std::string &fn, const QPGDeviceAdjoint *io, bool use_at, const QPGDevicePoint *at, const qpg_int *d_select,
+                       qpg_int *n_selected) {
   NEED_SETUP(bt, fn);
   if (!io || !io->gx) return fail(QPG_ERR_INVALID, fn + ": gx is NULL");
-  { const int rc = sens_refusals(bt, fn, io->active_in); if (rc != QPG_OK) return rc; }
+  const qpg_int *active_in;
+  { const int rc = sens_point(fn, use_at, at, io->active_in, &active_in); if (rc != QPG_OK) return rc; }
+  { const int rc = sens_refusals(bt, fn, active_in); if (rc != QPG_OK) return rc; }
   Subset sub;
   { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
   qpg_adjoint_args ar;
   memset(&ar, 0, sizeof(ar));
-  ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)io->active_in;
+  ar.gx = io->gx; ar.gy = io->gy; ar.active_in = (const int64_t *)active_in;
+  if (use_at) { ar.at_x = at->x; ar.at_y = at->y; }
   ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
   return sens_launch(bt, ar, io->dQx || io->dAx, sub);
 }
+extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) { return qpg_batch_adjoint_subset_device(bt, io, nullptr, nullptr); }
+extern "C" int qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const qpg_int *d_select, qpg_int *n_selected) {
+  return adjoint_run(bt, d_select ? "qpg_batch_adjoint_subset_device" : "qpg_batch_adjoint_device", io, false, nullptr, d_select, n_selected);
+}
+extern "C" int qpg_batch_adjoint_at_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected) {
+  return adjoint_run(bt, "qpg_batch_adjoint_at_device", io, true, at, d_select, n_selected);
+}
 /* The tangent of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 13): the adjoint's launch in its other mode -- the same kernel, set-up,
  * factor and refinement, on the right-hand side of a direction. */
-extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) { return qpg_batch_tangent_subset_device(bt, io, nullptr, nullptr); }
-extern "C" int qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected) {
-  const std::string fn = d_select ? "qpg_batch_tangent_subset_device" : "qpg_batch_tangent_device";
+static int tangent_run(qpg_batch *bt, const std::string &fn, const QPGDeviceTangent *io, bool use_at, const QPGDevicePoint *at, const qpg_int *d_select,
+                       qpg_int *n_selected) {
   NEED_SETUP(bt, fn);
   if (!io || (!io->dq && !io->dbmin && !io->dbmax && !io->dQx && !io->dAx)) return fail(QPG_ERR_INVALID, fn + ": no direction (dq, dbmin, dbmax, dQx and dAx are all NULL)");
-  { const int rc = sens_refusals(bt, fn, io->active_in); if (rc != QPG_OK) return rc; }
+  const qpg_int *active_in;
+  { const int rc = sens_point(fn, use_at, at, io->active_in, &active_in); if (rc != QPG_OK) return rc; }
+  { const int rc = sens_refusals(bt, fn, active_in); if (rc != QPG_OK) return rc; }
   Subset sub;
   { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
   qpg_adjoint_args ar;
   memset(&ar, 0, sizeof(ar));
-  ar.tangent = 1; ar.active_in = (const int64_t *)io->active_in;
+  ar.tangent = 1; ar.active_in = (const int64_t *)active_in;
+  if (use_at) { ar.at_x = at->x; ar.at_y = at->y; }
   ar.t_dq = io->dq; ar.t_dbmin = io->dbmin; ar.t_dbmax = io->dbmax; ar.t_dQx = io->dQx; ar.t_dAx = io->dAx;
   ar.dx = io->dx; ar.dy = io->dy;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
   return sens_launch(bt, ar, io->dQx || io->dAx, sub);
+}
+extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) { return qpg_batch_tangent_subset_device(bt, io, nullptr, nullptr); }
+extern "C" int qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected) {
+  return tangent_run(bt, d_select ? "qpg_batch_tangent_subset_device" : "qpg_batch_tangent_device", io, false, nullptr, d_select, n_selected);
+}
+extern "C" int qpg_batch_tangent_at_device(qpg_batch *bt, const QPGDeviceTangent *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected) {
+  return tangent_run(bt, "qpg_batch_tangent_at_device", io, true, at, d_select, n_selected);
+}
+/* The active set of the stored solutions on its own (include/qpalm_gfx950.h; k_get_active): what active_out of an adjoint call on this state holds */
+extern "C" int qpg_batch_get_active_device(qpg_batch *bt, qpg_int *d_active) { return qpg_batch_get_active_subset_device(bt, d_active, nullptr, nullptr); }
+extern "C" int qpg_batch_get_active_subset_device(qpg_batch *bt, qpg_int *d_active, const qpg_int *d_select, qpg_int *n_selected) {
+  const std::string fn = d_select ? "qpg_batch_get_active_subset_device" : "qpg_batch_get_active_device";
+  NEED_SETUP(bt, fn);
+  if (!d_active) return fail(QPG_ERR_INVALID, fn + ": d_active is NULL");
+  { const int rc = sens_refusals(bt, fn, nullptr); if (rc != QPG_OK) return rc; }
+  Subset sub;
+  { int rc; if (sens_select(bt, fn, d_select, n_selected, sub, rc)) return rc; }
+  BT_LAUNCH(bt, k_get_active, sub.blocks(bt), 0, bt->V, (int64_t *)d_active, sub.list);
+  if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_get_active failed: " + std::string(RT_LAST_ERROR()));
+  return api_ok();
 }
 /* The polish of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 14): the same launch in its third mode -- the correction of the stored
  * solution to the exact solution at its active set, a verdict per member and, with store, the accepted candidates as the new stored solutions. */

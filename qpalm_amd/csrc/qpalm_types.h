@@ -185,6 +185,9 @@ typedef struct {
   /* the penalty floor of the refinement's preconditioner (qpg_batch_set_sens_penalty): sigma'_i = max(sigma_i, sens_floor) on the rows of J; 0 = the
    * solve's own penalties */
   double sens_floor;
+  /* at_x != NULL: the call is qpg_batch_adjoint_at_device / qpg_batch_tangent_at_device (QPGDevicePoint): the point is the caller's [B][n] / [B][m] arrays
+   * instead of the stored solutions, active_in (required then) is its active set, and the members' statuses are not consulted */
+  const double *at_x, *at_y;
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

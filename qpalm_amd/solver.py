@@ -98,6 +98,9 @@ class QpalmBatch:
         self.nnzA, self.nnzQ = nnzA, nnzQ   # row lengths of the arrays update_Q_A takes
         self.settings = settings if settings is not None else ctx.default_settings()
         self.epoch = 0   # counts the calls that change what adjoint_device differentiates (solves, warm starts, updates): torch_layer checks it
+        # counts the calls that change the values of Q and A (a setup, update_Q_A*): a point recorded under another count is no longer valid for
+        # adjoint_device / tangent_device(at=...)
+        self.matrix_epoch = 1
         h = C.c_void_p()
         import time
         t0 = time.perf_counter()
@@ -237,12 +240,14 @@ class QpalmBatch:
         given with.  [B][nnzQ_max] / [B][nnzA_max] arrays, or lists of per-member arrays.  The batch is then what a fresh setup with these values, the
         latest q / bounds and the current settings would be; the stored solutions stay (warm_start_last)."""
         self.epoch += 1
+        self.matrix_epoch += 1
         q, a = self._padded(Qx, self.nnzQ), self._padded(Ax, self.nnzA)
         self._check(self.L.qpg_batch_update_Q_A(self.h, fptr(q), fptr(a)))
 
     def update_Q_A_device(self, ptr_Qx, ptr_Ax):
         """the same from device memory: raw addresses of [B][nnzQ_max] / [B][nnzA_max] float64 arrays (e.g. torch tensors' data_ptr())"""
         self.epoch += 1
+        self.matrix_epoch += 1
         self._check(self.L.qpg_batch_update_Q_A_device(self.h, C.c_void_p(int(ptr_Qx)), C.c_void_p(int(ptr_Ax))))
 
     # -- the per-step calls on arrays in device memory ---------------------------------------------------
@@ -329,6 +334,39 @@ class QpalmBatch:
         rc = getattr(self.L, "qpg_batch_%s_subset_device" % name)(self.h, C.byref(io), sel, C.byref(cnt))
         return rc, int(cnt.value)
 
+    def _sens_call(self, name, io, select, at):
+        """_subset_call, or with at = (x, y, active) the call at a recorded point (qpg_batch_<name>_at_device, which takes select itself)"""
+        if at is None:
+            return self._subset_call(name, io, select)
+        if not isinstance(at, (tuple, list)) or len(at) != 3 or any(v is None for v in at):
+            raise ValueError("at: expected (x, y, active), all three given")
+        if select is not None and (isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr")):
+            raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
+        x, y, act, sel = self._dev_args((at[0], (self.B, self.n), "at x", "float64"), (at[1], (self.B, self.m), "at y", "float64"),
+                                        (at[2], (self.B, self.m), "at active", "int64"), (select, (self.B,), "select", "int64"))
+        cnt = capi.c_int(0)
+        rc = getattr(self.L, "qpg_batch_%s_at_device" % name)(self.h, C.byref(io), C.byref(capi.DevicePoint(x, y, act)), sel, C.byref(cnt))
+        return rc, int(cnt.value)
+
+    def active_device(self, out=None, select=None):
+        """The active set of the stored solutions ([B][m] int64 in device memory: -1 lower, +1 upper, 0 inactive; all zeros for a member that is not
+        SOLVED / DUAL_TERMINATED) by the rule adjoint_device applies with active=None (qpg_batch_get_active_device): what its `active` output would
+        hold, without the solve.  out: a tensor or raw address to fill, else a new tensor.  select: as for step_device -- only the rows of members with
+        1 are written.  With x, y of solution_device it is the point `at=` of adjoint_device / tangent_device takes.  `epoch` stays."""
+        if out is None:
+            out = self._empty((self.B, self.m), "int64")
+            if select is not None:
+                out.zero_()
+        a, = self._dev_args((out, (self.B, self.m), "out", "int64"))
+        if select is None:
+            self._check(self.L.qpg_batch_get_active_device(self.h, a))
+        else:
+            if isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr"):
+                raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
+            sel, = self._dev_args((select, (self.B,), "select", "int64"))
+            self._check(self.L.qpg_batch_get_active_subset_device(self.h, a, sel, None))
+        return out
+
     def step_device(self, bmin=None, bmax=None, q=None, warm="last", out=None, select=None):
         """One receding-horizon step without the host (qpg_batch_step_device): new bounds / q (None = unchanged), warm start ("last" = every QP's own
         last solution, None = none, (x, y) = given arrays, one of which may be None), solve, and the results written in device memory.  All arrays are
@@ -373,14 +411,18 @@ class QpalmBatch:
 
     ADJOINT_OUT = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
 
-    def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None):
+    def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None, at=None):
         """Gradients of a loss through the stored solutions (qpg_batch_adjoint_device): gx = dl/dx [B][n], gy = dl/dy [B][m] or None, active = the active
         set to differentiate at ([B][m] int64: -1 lower, +1 upper, 0 inactive) or None for the engine's own test on the stored solution.  All arrays
         are torch tensors on the context's device or raw addresses.  want: which outputs to compute, among dq [B][n], dbmin / dbmax [B][m],
         dQx [B][nnzQ_max], dAx [B][nnzA_max] (the layout update_Q_A takes), active [B][m] int64 (the set used), flag [B] int64 (0 done, 1 pass cap /
         non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses to fill instead (then `want` is ignored).
         Returns the dict.  select: as for step_device -- only the members with 1 are differentiated (qpg_batch_adjoint_subset_device); the rows of the
-        others in every output, flag included, keep what they held, and the dict gains n_selected."""
+        others in every output, flag included, keep what they held, and the dict gains n_selected.
+        at: None, or (x, y, active) -- a point recorded after an earlier solve of this batch (solution_device and active_device, or the `active` output
+        of a sensitivity call made then): the gradients are those of THAT solve (qpg_batch_adjoint_at_device), however often the
+        batch has been stepped since.  Valid while `matrix_epoch` is what it was at that solve; q, bounds, penalties and warm starts may differ.  The
+        members' current statuses are not consulted (no flag 2): exclude members with select.  `active` must be None then."""
         nB, n, m = self.B, self.n, self.m
         shapes = dict(dq=((nB, n), "float64"), dbmin=((nB, m), "float64"), dbmax=((nB, m), "float64"), dQx=((nB, self.nnzQ), "float64"),
                       dAx=((nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
@@ -395,7 +437,7 @@ class QpalmBatch:
         a = self._dev_args((gx, (nB, n), "gx", "float64"), (gy, (nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
                            *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
         io = capi.DeviceAdjoint(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11])
-        rc, cnt = self._subset_call("adjoint", io, select)
+        rc, cnt = self._sens_call("adjoint", io, select, at)
         self._check(rc)
         if select is not None:
             out["n_selected"] = cnt
@@ -403,14 +445,14 @@ class QpalmBatch:
 
     TANGENT_OUT = ("dx", "dy", "active", "flag", "resid", "passes")
 
-    def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None):
+    def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None, at=None):
         """How the stored solutions move along one direction of the data (qpg_batch_tangent_device): dq [B][n], dbmin / dbmax [B][m], dQx [B][nnzQ_max],
         dAx [B][nnzA_max] (the layout update_Q_A takes); None = zero, at least one must be given.  active: as for adjoint_device.  All arrays are torch
         tensors on the context's device or raw addresses.  want: which outputs to compute, among dx [B][n], dy [B][m], active [B][m] int64 (the set
         used), flag [B] int64 (0 done, 1 pass cap / non-finite, 2 member not solved), resid [B], passes [B] int64.  out: a dict of tensors / addresses
         to fill instead (then `want` is ignored).  Returns the dict.  The batch's state (and `epoch`) stays: x + dx, y + dy is a first-order
         prediction of the next solution and can go straight into warm_start_device.  select: as for adjoint_device
-        (qpg_batch_tangent_subset_device)."""
+        (qpg_batch_tangent_subset_device).  at: as for adjoint_device (qpg_batch_tangent_at_device)."""
         nB, n, m = self.B, self.n, self.m
         shapes = dict(dx=((nB, n), "float64"), dy=((nB, m), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
                       passes=((nB,), "int64"))
@@ -425,7 +467,7 @@ class QpalmBatch:
                            (dQx, (nB, self.nnzQ), "dQx", "float64"), (dAx, (nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
                            *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
         io = capi.DeviceTangent(*a)
-        rc, cnt = self._subset_call("tangent", io, select)
+        rc, cnt = self._sens_call("tangent", io, select, at)
         self._check(rc)
         if select is not None:
             out["n_selected"] = cnt

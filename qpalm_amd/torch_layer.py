@@ -24,8 +24,17 @@ layer(q, ..., select=s) with s a [B] int64 tensor of 0 / 1 steps only the member
 status are still those of every member: the rows of the others are their stored solutions and statuses from before.  backward and jvp pass the same
 select on, so those members cost nothing there and get zero gradients and tangents; with polish=True only the selected members are polished.  The rows of
 `last_adjoint`, `last_tangent` and `last_polish` (flag, resid, passes, res) mean something for the selected members only; the others read zero.  Input rows
-of members that are not selected are not read at all.  A subset forward needs every output row it returns to exist, so call it after a full forward or solve."""
+of members that are not selected are not read at all.  A subset forward needs every output row it returns to exist, so call it after a full forward or solve.
+
+QPLayer(batch, replay=True) lifts the "backward before the next solve" rule: every forward also records its point -- x, y, the
+active set (QpalmBatch.active_device, or the polish's own with polish=True) and the statuses -- and backward() differentiates at that record
+(QpalmBatch.adjoint_device(at=...)) instead of at whatever the batch holds by then.  One batch can so be stepped T times, each q / bounds computed from the
+solution before, and one backward() goes through the whole rollout.  The record is valid as long as the values of Q and A are those of its solve:
+backward() raises RuntimeError only if `QpalmBatch.matrix_epoch` moved (update_Q_A*, in this layer through Qx= / Ax=).  Members whose recorded status was
+not SOLVED / DUAL_TERMINATED get zero gradients, as without replay.  Forward mode (jvp) runs inside the forward pass and is the same with and without."""
 import torch
+
+from .solver import SOLVED, DUAL_TERMINATED
 
 
 class _QPFunction(torch.autograd.Function):
@@ -51,11 +60,21 @@ class _QPFunction(torch.autograd.Function):
             raise ValueError("QPLayer: some member's bounds were refused (bmin > bmax): %r" % out["rejected"].nonzero().flatten().tolist())
         if layer.polish:
             # accepted members: the exact solution at their active set, returned and stored -- backward and jvp differentiate at the stored solution
-            pol = bt.polish_device(store=True, select=select,
-                                   out=dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
-                                            resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_()))
+            pol_out = dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
+                           resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_())
+            if layer.replay:   # the set the polish used: the recorded point's active set
+                pol_out["active"] = bt._empty((bt.B, bt.m), "int64").zero_()
+            pol = bt.polish_device(store=True, select=select, out=pol_out)
             layer.last_polish = {k: pol[k] for k in ("flag", "res", "resid", "passes")}
         fctx.layer, fctx.epoch, fctx.select = layer, bt.epoch, select
+        fctx.replay = layer.replay
+        if layer.replay:   # the point of THIS solve, for a backward() that may come any number of steps later
+            if layer.polish:
+                active = pol["active"]
+            else:
+                active = bt.active_device(out=bt._empty((bt.B, bt.m), "int64").zero_(), select=select)
+            fctx.save_for_backward(out["x"], out["y"])
+            fctx.active, fctx.status_val, fctx.matrix_epoch = active, out["status_val"].clone(), bt.matrix_epoch
         fctx.mark_non_differentiable(out["status_val"])
         return out["x"], out["y"], out["status_val"]
 
@@ -63,6 +82,8 @@ class _QPFunction(torch.autograd.Function):
     def backward(fctx, gx, gy, _gs):
         layer = fctx.layer
         bt = layer.batch
+        if fctx.replay:
+            return _QPFunction._backward_replay(fctx, gx, gy)
         if bt.epoch != fctx.epoch:
             raise RuntimeError("QPLayer.backward: the batch was solved or updated again after this forward pass; its gradients are gone")
         need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
@@ -75,6 +96,28 @@ class _QPFunction(torch.autograd.Function):
             shapes = dict(dq=(bt.B, bt.n), dbmin=(bt.B, bt.m), dbmax=(bt.B, bt.m), dQx=(bt.B, bt.nnzQ), dAx=(bt.B, bt.nnzA), flag=(bt.B,), resid=(bt.B,), passes=(bt.B,))
             zeros = {k: bt._empty(shapes[k], "int64" if k in ("flag", "passes") else "float64").zero_() for k in want}
             out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=zeros, select=select)
+        layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
+        return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx")) + (None,)
+
+    @staticmethod
+    def _backward_replay(fctx, gx, gy):
+        """backward at the recorded point of this forward pass: the batch may have been stepped any number of times since"""
+        layer = fctx.layer
+        bt = layer.batch
+        if bt.matrix_epoch != fctx.matrix_epoch:
+            raise RuntimeError("QPLayer.backward: the values of Q and A were updated after this forward pass; its recorded point is no longer valid")
+        x, y = fctx.saved_tensors
+        need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
+        want = tuple(k for k, v in need.items() if v) + ("flag", "resid", "passes")
+        gx = bt._empty((bt.B, bt.n)).zero_() if gx is None else gx.contiguous()
+        # the recorded statuses decide who is differentiated (the current ones are those of a later solve); the others keep zero rows
+        select = ((fctx.status_val == SOLVED) | (fctx.status_val == DUAL_TERMINATED)).to(torch.int64)
+        if fctx.select is not None:
+            select = select * (fctx.select != 0).to(torch.int64)
+        shapes = dict(dq=(bt.B, bt.n), dbmin=(bt.B, bt.m), dbmax=(bt.B, bt.m), dQx=(bt.B, bt.nnzQ), dAx=(bt.B, bt.nnzA), flag=(bt.B,), resid=(bt.B,), passes=(bt.B,))
+        zeros = {k: bt._empty(shapes[k], "int64" if k in ("flag", "passes") else "float64").zero_() for k in want}
+        out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=zeros, select=select.contiguous(),
+                                at=(x.detach().contiguous(), y.detach().contiguous(), fctx.active))
         layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
         return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx")) + (None,)
 
@@ -104,14 +147,16 @@ class QPLayer(torch.nn.Module):
     """x*(q, bmin, bmax[, Qx, Ax]) of a set-up QpalmBatch as a torch module.  warm: the warm start of every forward step, as step_device takes it
     (None = cold, "last" = every member's previous solution).  polish: polish every forward solve and store the result (see above).  sens_penalty: a
     number sets the batch's penalty floor for the adjoint, tangent and polish solves (QpalmBatch.sens_penalty); None leaves the
-    batch's value alone."""
+    batch's value alone.  replay: record every forward's point and differentiate there, so that backward() may come after later solves of the same batch
+    (see above)."""
 
-    def __init__(self, batch, warm=None, polish=False, sens_penalty=None):
+    def __init__(self, batch, warm=None, polish=False, sens_penalty=None, replay=False):
         super().__init__()
         if sens_penalty is not None:
             batch.sens_penalty = sens_penalty
         self.batch, self.warm, self.last_adjoint, self.last_tangent = batch, warm, None, None
         self.polish, self.last_polish = bool(polish), None
+        self.replay = bool(replay)
 
     def forward(self, q=None, bmin=None, bmax=None, Qx=None, Ax=None, select=None):
         return _QPFunction.apply(self, q, bmin, bmax, Qx, Ax, select)
