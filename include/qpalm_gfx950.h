@@ -436,6 +436,27 @@ typedef struct {
 } QPGDevicePoint;
 int  qpg_batch_adjoint_at_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
 int  qpg_batch_tangent_at_device(qpg_batch *bt, const QPGDeviceTangent *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
+/* ---- K directions per call: the adjoint for K pairs (gx, gy) and the tangent for K directions of the data, in one call.  What
+ * does not depend on the direction is done once per call or per member -- the check for a solve in progress, the check of active_in, the selection, the
+ * launch, the active set, ||K||inf and the fresh factor -- and a member's K right-hand sides are then refined one after another on that factor.
+ * Layout: every per-direction array is K consecutive blocks of the single call's array, direction-major, so slice k IS a single call's array:
+ *   gx, dq (both calls), dx                  [K][B][n]
+ *   gy, dbmin, dbmax (both calls), dy        [K][B][m]
+ *   dQx / dAx (both calls)                   [K][B][nnzQ_max] / [K][B][nnzA_max]
+ *   flag, resid, passes                      [K][B]
+ *   active_in, active_out, at->x, at->y, at->active, d_select      as in the single calls, shared by all directions (active_out is written once)
+ * A NULL direction array is zero in every direction.  at = NULL: the stored solutions (as qpg_batch_*_subset_device); otherwise the recorded point (as
+ * qpg_batch_*_at_device).  d_select = NULL: every member.  n_selected as in the subset forms.
+ * CONTRACT: slice k of every output is bit for bit what the corresponding single call (qpg_batch_*_device, *_subset_device or *_at_device) returns for
+ * slice k of the inputs on the same state, with the same active_in / at / d_select and the same penalty floor.  flag, resid and passes are per
+ * direction: a direction that reaches the pass cap or is not finite gets flag 1 and zeros in ITS slice only.  A member that is not SOLVED /
+ * DUAL_TERMINATED (flag 2), or whose recorded point is not finite (flag 1), gets that flag and zeros in all K slices.  A member that is not selected
+ * has none of its rows written in any slice.  State: as for the single calls -- solve -> multi call -> step is bit for bit solve -> step.  The polish has
+ * no K form.
+ * QPG_ERR_INVALID: K < 1, and whatever the single call refuses, checked once per call (for the tangent: all five direction arrays NULL; for the
+ * adjoint: gx = NULL); QPG_ERR_UNSUPPORTED: exactly the single calls' refusals. */
+int  qpg_batch_adjoint_multi_device(qpg_batch *bt, const QPGDeviceAdjoint *io, qpg_int K, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
+int  qpg_batch_tangent_multi_device(qpg_batch *bt, const QPGDeviceTangent *io, qpg_int K, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected);
 int  qpg_batch_get_info(qpg_batch *bt, qpg_int idx, QPGInfo *out);
 int  qpg_batch_get_stats(qpg_batch *bt, qpg_int idx, QPGStats *out);
 int  qpg_batch_get_info_all(qpg_batch *bt, QPGInfo *out /* [B] */);   /* QPALMInfo of every QP (what the multi-GPU gather sends) */

@@ -45,6 +45,10 @@
  * of Q and A are still its own.  qpg_adjoint_args.at_x / at_y replace sol_x / sol_y wherever dev_adjoint hands a point on, J is active_in, and the
  * member's status -- that of a later solve -- is not consulted.  k_get_active gives the J of the stored solutions on its own, by sens_setup's rule.
  *
+ * Several directions per call (qpg_batch_adjoint_multi_device / qpg_batch_tangent_multi_device): sens_setup does not depend on the
+ * right-hand side, so dev_adjoint runs it once per member and then, for each of qpg_adjoint_args.ndir directions in turn, the right-hand side,
+ * sens_refine and the outputs on slice k of the per-direction arrays.  The arithmetic of a direction is that of the single call: slice k holds its bits.
+ *
  * Scratch: vectors a finished solve leaves behind and the next one rebuilds before it reads them (d, temp_n, delta_x, dphi, z, temp_m, delta_y,
  * the line-search scratch, enter / leave) and the workgroup's factor slot.  The active flags form_schur / sp_factor read are saved and put back
  * (update_sigma of a later solve may read them before its first Newton step).  x, y, the stored solution, sigma, gamma, Qx / Ax products and
@@ -214,10 +218,11 @@ QPD void tan_gather_rows(int nrows, const int *__restrict__ ptr, const int *__re
   }
 }
 
-/* ---- the adjoint's right-hand side: [c D gx; E gy_J] ---- */
-QPN void adj_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, const IterShared &I) {
+/* ---- the adjoint's right-hand side: [c D gx; E gy_J], of direction k (MULTI = false: the only one) ---- */
+template <bool MULTI>
+QPN void adj_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, int b, int k, const IterShared &I) {
   const int n = a.n, m = a.m, tid = threadIdx.x, scal = I.s.has_scaling;
-  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  const size_t on = (MULTI ? (size_t)k * (size_t)io.dir_n : 0) + (size_t)b * V.n, om = (MULTI ? (size_t)k * (size_t)io.dir_m : 0) + (size_t)b * V.m;
   const double c = I.s.sc_c;
   for (int j = tid; j < n; j += QP_T) {
     const double g = io.gx[on + j];
@@ -235,15 +240,18 @@ QPN void adj_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const 
 /* ---- the tangent's right-hand side: r1 = -(dq + dQ x + dA' y), r2_i = db_i - (dA x)_i on J, formed in unscaled space from the
  * point (x, y: the stored solution, or the caller's recorded one) and the caller's directions, then [c D r1; E r2].  y is that of every row.  dQx / dAx
  * are read where the caller put them (k_update_Q_A's maps): dA' y by the columns of A, dQ x by the rows of the full symmetric pattern (Qfperm: a stored lower entry stands for both
- * positions; upper entries of the caller are in no map), dA x by the rows of A' (Atperm) -- gathers, eight lanes per column / row. ---- */
-QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, const double *x, const double *y, int b,
+ * positions; upper entries of the caller are in no map), dA x by the rows of A' (Atperm) -- gathers, eight lanes per column / row.  kd: the direction
+ * (slice kd of the five direction arrays; MULTI = false: the only one). ---- */
+template <bool MULTI>
+QPN void tan_rhs(const qpg_view &V, const QpArrays &a, const SensVecs &v, const qpg_adjoint_args &io, const double *x, const double *y, int b, int kd,
                  const IterShared &I) {
   const int n = a.n, m = a.m, scal = I.s.has_scaling;
-  const size_t on = (size_t)b * V.n, om = (size_t)b * V.m;
+  const size_t on = (MULTI ? (size_t)kd * (size_t)io.dir_n : 0) + (size_t)b * V.n, om = (MULTI ? (size_t)kd * (size_t)io.dir_m : 0) + (size_t)b * V.m;
   const double c = I.s.sc_c;
   const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1, sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
   const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr, *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
-  const double *dA = io.t_dAx ? io.t_dAx + (size_t)b * io.strideA : nullptr, *dQ = io.t_dQx ? io.t_dQx + (size_t)b * io.strideQ : nullptr;
+  const double *dA = io.t_dAx ? io.t_dAx + ((MULTI ? (size_t)kd * (size_t)io.dir_A : 0) + (size_t)b * io.strideA) : nullptr;
+  const double *dQ = io.t_dQx ? io.t_dQx + ((MULTI ? (size_t)kd * (size_t)io.dir_Q : 0) + (size_t)b * io.strideQ) : nullptr;
   const int *Atperm = a.Atperm(), *Qfperm = a.Qfperm();
   double *r1 = v.r1;
   auto all = [](int) { return true; };
@@ -386,8 +394,10 @@ QPN void pol_finish(const qpg_view &V, const QpArrays &a, const SensVecs &v, con
   __syncthreads();
 }
 
-/* One member of k_adjoint: the adjoint, the tangent (io.tangent) or the polish (io.polish).  They differ in the right-hand side and in what they write. */
-template <int RPT>
+/* One member of k_adjoint: the adjoint, the tangent (io.tangent) or the polish (io.polish).  They differ in the right-hand side and in what they write.
+ * MULTI = false (k_adjoint, the single calls): one direction and no distance between directions, known to the compiler -- the loop below and its
+ * offsets fold away.  MULTI = true (k_adjoint_multi): io.ndir directions, io.dir_* apart. */
+template <int RPT, bool MULTI>
 QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int slot, IterShared &I, char *lds) {
   const QpArrays a = qp_arrays(V, b);
   const int n = a.n, m = a.m, tid = threadIdx.x;
@@ -402,9 +412,9 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
   const bool at = (io.at_x != nullptr);
   const double *px = at ? io.at_x + on : a.sol_x(), *py = at ? io.at_y + om : a.sol_y();
   const int status = QP_UNIFORM(I.s.status);
-  int flag = (at || status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
-  int passes = 0;
-  double ratio = 0.0, pri_old = 0.0, dua_old = 0.0;
+  /* the member's own flag: 2 = not solved, 1 = a recorded point that is not finite; every direction of such a member gets it, and zeros */
+  int mflag = (at || status == QPG_SOLVED || status == QPG_DUAL_TERMINATED) ? 0 : 2;
+  double normK = 0.0, pri_old = 0.0, dua_old = 0.0;
   const SensVecs v = sens_vecs(a);
   double *u = v.u, *w = v.w;
   int *sgn = v.sgn;
@@ -414,80 +424,95 @@ QPN void dev_adjoint(const qpg_view &V, const qpg_adjoint_args &io, int b, int s
     for (int i = tid; i < m; i += QP_T) vs[0] += (double)adj_bad(py[i]);
     block_reduce<0, 1>(I.S, vs, vs);
     if (QP_UNIFORM((int)(vs[0] != 0.0))) {
-      flag = 1;
+      mflag = 1;
       for (int i = tid; i < m; i += QP_T) { const int64_t av = io.active_in[om + i]; sgn[i] = (av < 0) ? -1 : ((av > 0) ? 1 : 0); }
       __syncthreads();
     }
   }
-  if (flag == 0) {
-    const double normK = sens_setup<RPT>(V, a, v, px, py, io.active_in, b, slot, I, lds, sfloor);
-    if (polish) pol_rhs(V, a, v, I, pri_old, dua_old);
-    else if (tangent) tan_rhs(V, a, v, io, px, py, b, I);
-    else adj_rhs(V, a, v, io, b, I);
-    sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, sfloor, flag, passes, ratio);
-  }
-  if (polish) pol_finish(V, a, v, io, b, I, flag, pri_old, dua_old); /* (x, y, res and the store; the outputs below that a polish has are written there) */
-  /* ---- outputs; whole strides: entries beyond the member's own n / m are zeros ---- */
-  const bool ok = (flag == 0);
-  if (tangent) {
-    if (io.dx) for (int j = tid; j < V.n; j += QP_T) io.dx[on + j] = (ok && j < n) ? u[j] : 0.0;
-    if (io.dy) for (int i = tid; i < V.m; i += QP_T) io.dy[om + i] = (ok && i < m && sgn[i]) ? w[i] : 0.0;
-  } else if (io.dq) for (int j = tid; j < V.n; j += QP_T) io.dq[on + j] = (ok && j < n) ? -u[j] : 0.0;
-  for (int i = tid; i < V.m; i += QP_T) {
-    const int sg = (flag != 2 && i < m) ? sgn[i] : 0;
-    const double wv = (ok && i < m) ? w[i] : 0.0;
-    if (io.dbmin) io.dbmin[om + i] = (sg < 0) ? wv : 0.0;
-    if (io.dbmax) io.dbmax[om + i] = (sg > 0) ? wv : 0.0;
-    if (io.active_out) io.active_out[om + i] = sg;
-  }
-  if (tid == 0) {
-    if (io.flag) io.flag[b] = flag;
-    if (io.resid) io.resid[b] = ratio;
-    if (io.passes) io.passes[b] = passes;
-  }
-  /* ---- the per-entry gradients, in the order qpg_batch_update_Q_A takes its values (k_update_Q_A's maps, the other way round); eight lanes per column ---- */
-  if (io.dAx) {
-    double *o = io.dAx + (size_t)b * io.strideA;
-    for (int64_t k = tid; k < io.strideA; k += QP_T) o[k] = 0.0;
-    __syncthreads();
-    if (ok) {
-      const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1;
-      const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr;
-      for (int j = tid >> 3; j < n; j += QP_T >> 3) {
-        const double uj = u[j], xj = px[j];
-        for (int k = a.Ap()[j] + (tid & 7); k < a.Ap()[j + 1]; k += 8) {
-          const int i = a.Ai()[k];
-          o[sameA ? k : mA[k]] = -(py[i] * uj + w[i] * xj);
+  if (mflag == 0) normK = sens_setup<RPT>(V, a, v, px, py, io.active_in, b, slot, I, lds, sfloor);
+  /* ---- the directions, one after another on the factor sens_setup left.  Each starts where the single call's only one starts:
+   * z = 0 (sens_setup for the first, the loop for the others), and every other vector of SensVecs is written before it is read -- r1 / r2 by the
+   * right-hand side, xs, r1, r2, t by a pass of sens_refine.  sens_refine puts the saved active flags back after every direction; nothing from there
+   * to the next direction's refinement reads them (adj_rhs, tan_rhs, the refinement and the two solves go by sgn and the factor). ---- */
+  const int ndir = MULTI ? QP_UNIFORM(io.ndir) : 1;
+  for (int kd = 0; kd < ndir; kd++) {
+    const size_t dn = (MULTI ? (size_t)kd * (size_t)io.dir_n : 0) + on, dm = (MULTI ? (size_t)kd * (size_t)io.dir_m : 0) + om;
+    const size_t db = (MULTI ? (size_t)kd * (size_t)io.dir_b : 0) + (size_t)b;
+    int flag = mflag, passes = 0;
+    double ratio = 0.0;
+    if (mflag == 0) {
+      if (kd > 0) {
+        for (int j = tid; j < n; j += QP_T) u[j] = 0.0;
+        for (int i = tid; i < m; i += QP_T) w[i] = 0.0;
+        __syncthreads();
+      }
+      if (polish) pol_rhs(V, a, v, I, pri_old, dua_old);
+      else if (tangent) tan_rhs<MULTI>(V, a, v, io, px, py, b, kd, I);
+      else adj_rhs<MULTI>(V, a, v, io, b, kd, I);
+      sens_refine<RPT>(V, a, v, b, slot, I, lds, normK, io.max_pass, sfloor, flag, passes, ratio);
+    }
+    if (polish) pol_finish(V, a, v, io, b, I, flag, pri_old, dua_old); /* (x, y, res and the store; the outputs below that a polish has are written there) */
+    /* ---- outputs of the direction; whole strides: entries beyond the member's own n / m are zeros ---- */
+    const bool ok = (flag == 0);
+    if (tangent) {
+      if (io.dx) for (int j = tid; j < V.n; j += QP_T) io.dx[dn + j] = (ok && j < n) ? u[j] : 0.0;
+      if (io.dy) for (int i = tid; i < V.m; i += QP_T) io.dy[dm + i] = (ok && i < m && sgn[i]) ? w[i] : 0.0;
+    } else if (io.dq) for (int j = tid; j < V.n; j += QP_T) io.dq[dn + j] = (ok && j < n) ? -u[j] : 0.0;
+    for (int i = tid; i < V.m; i += QP_T) {
+      const int sg = (flag != 2 && i < m) ? sgn[i] : 0;
+      const double wv = (ok && i < m) ? w[i] : 0.0;
+      if (io.dbmin) io.dbmin[dm + i] = (sg < 0) ? wv : 0.0;
+      if (io.dbmax) io.dbmax[dm + i] = (sg > 0) ? wv : 0.0;
+      if (io.active_out && kd == 0) io.active_out[om + i] = sg; /* (the set is the member's, not the direction's) */
+    }
+    if (tid == 0) {
+      if (io.flag) io.flag[db] = flag;
+      if (io.resid) io.resid[db] = ratio;
+      if (io.passes) io.passes[db] = passes;
+    }
+    /* ---- the per-entry gradients, in the order qpg_batch_update_Q_A takes its values (k_update_Q_A's maps, the other way round); eight lanes per column ---- */
+    if (io.dAx) {
+      double *o = io.dAx + ((MULTI ? (size_t)kd * (size_t)io.dir_A : 0) + (size_t)b * io.strideA);
+      for (int64_t k = tid; k < io.strideA; k += QP_T) o[k] = 0.0;
+      __syncthreads();
+      if (ok) {
+        const int sameA = io.same ? QP_UNIFORM(io.same[2 * b]) : 1;
+        const int32_t *mA = io.mapA ? io.mapA + (size_t)b * V.nnzA : nullptr;
+        for (int j = tid >> 3; j < n; j += QP_T >> 3) {
+          const double uj = u[j], xj = px[j];
+          for (int k = a.Ap()[j] + (tid & 7); k < a.Ap()[j + 1]; k += 8) {
+            const int i = a.Ai()[k];
+            o[sameA ? k : mA[k]] = -(py[i] * uj + w[i] * xj);
+          }
         }
       }
     }
-  }
-  if (io.dQx) {
-    double *o = io.dQx + (size_t)b * io.strideQ;
-    for (int64_t k = tid; k < io.strideQ; k += QP_T) o[k] = 0.0;
-    __syncthreads();
-    if (ok) {
-      const int sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
-      const int32_t *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
-      for (int j = tid >> 3; j < n; j += QP_T >> 3) {
-        const double uj = u[j], xj = px[j];
-        for (int k = a.Qp()[j] + (tid & 7); k < a.Qp()[j + 1]; k += 8) {
-          const int i = a.Qi()[k]; /* i >= j: the stored entry stands for both symmetric positions */
-          o[sameQ ? k : mQ[k]] = (i == j) ? -(uj * xj) : -(u[i] * xj + uj * px[i]);
+    if (io.dQx) {
+      double *o = io.dQx + ((MULTI ? (size_t)kd * (size_t)io.dir_Q : 0) + (size_t)b * io.strideQ);
+      for (int64_t k = tid; k < io.strideQ; k += QP_T) o[k] = 0.0;
+      __syncthreads();
+      if (ok) {
+        const int sameQ = io.same ? QP_UNIFORM(io.same[2 * b + 1]) : 1;
+        const int32_t *mQ = io.mapQ ? io.mapQ + (size_t)b * V.nnzQ : nullptr;
+        for (int j = tid >> 3; j < n; j += QP_T >> 3) {
+          const double uj = u[j], xj = px[j];
+          for (int k = a.Qp()[j] + (tid & 7); k < a.Qp()[j + 1]; k += 8) {
+            const int i = a.Qi()[k]; /* i >= j: the stored entry stands for both symmetric positions */
+            o[sameQ ? k : mQ[k]] = (i == j) ? -(uj * xj) : -(u[i] * xj + uj * px[i]);
+          }
         }
       }
     }
+    __syncthreads(); /* (u and w have been read: the next direction may zero them) */
   }
-  __syncthreads();
 }
 
 /* One workgroup per factor slot; the members come off the work queue (V.queue[0], zeroed by the host) as in k_solve, so B > slots works.
  * io.list: the members of a subset call, through the same queue (everything dev_adjoint touches is the member's own or the workgroup's slot).
- * RPT = QPG_RPT_SPARSE: the sparse factor (sp_factor / sp_solve); any other value: the dense panel. */
-template <int RPT>
-__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_adjoint_args io) {
-  __shared__ IterShared I;
-  char *lds = QP_DYN_LDS();
+ * RPT = QPG_RPT_SPARSE: the sparse factor (sp_factor / sp_solve); any other value: the dense panel.
+ * k_adjoint: the single calls (one direction per member, the code the compiler made of it before there were several); k_adjoint_multi: io.ndir > 1. */
+template <int RPT, bool MULTI>
+QPD void adjoint_queue(const qpg_view &V, const qpg_adjoint_args &io, IterShared &I, char *lds) {
   while (true) {
     __syncthreads();
     if (threadIdx.x == 0) I.S.ibc[0] = atomicAdd(V.queue, 1);
@@ -495,8 +520,18 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_a
     int b = QP_UNIFORM(I.S.ibc[0]);
     if (b < V.B && io.list != nullptr) b = QP_UNIFORM(io.list[b]); /* a subset: the listed members, then B (k_select) */
     if (b >= V.B) break;
-    dev_adjoint<RPT>(V, io, b, blockIdx.x, I, lds);
+    dev_adjoint<RPT, MULTI>(V, io, b, blockIdx.x, I, lds);
   }
+}
+template <int RPT>
+__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint(qpg_view V, qpg_adjoint_args io) {
+  __shared__ IterShared I;
+  adjoint_queue<RPT, false>(V, io, I, QP_DYN_LDS());
+}
+template <int RPT>
+__global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_adjoint_multi(qpg_view V, qpg_adjoint_args io) {
+  __shared__ IterShared I;
+  adjoint_queue<RPT, true>(V, io, I, QP_DYN_LDS());
 }
 
 /* qpg_batch_get_active_device: the active set of the stored solutions by the rule of sens_setup (sens_active_row on t = A~ x~), into the caller's [B][m]

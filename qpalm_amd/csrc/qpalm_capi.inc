@@ -2064,9 +2064,15 @@ static int sens_refusals(qpg_batch *bt, const std::string &fn, const qpg_int *ac
   }
   return QPG_OK;
 }
-/* the launch of k_adjoint (either mode); maps: the call reads or writes per-entry arrays in the caller's order */
-static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps, const Subset &sub) {
+/* the launch of k_adjoint (either mode); maps: the call reads or writes per-entry arrays in the caller's order.  K directions per member (DESIGN.md
+ * section 18): the per-direction arrays are K blocks of the single call's layout; the single calls have K = 1 and no distance between directions */
+static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps, const Subset &sub, qpg_int K = 1) {
   ar.strideQ = bt->nnzQ_in; ar.strideA = bt->nnzA_in; ar.max_pass = QPG_ADJOINT_MAX_PASS; ar.sens_floor = bt->sens_floor;
+  ar.ndir = (int32_t)K;
+  if (K > 1) {
+    const int64_t nB = bt->B;
+    ar.dir_n = nB * bt->V.n; ar.dir_m = nB * bt->V.m; ar.dir_Q = nB * ar.strideQ; ar.dir_A = nB * ar.strideA; ar.dir_b = nB;
+  }
   if (maps) {
     int32_t *mapA_d, *mapQ_d, *same_d;
     const int rcm = value_maps_device(bt, &mapA_d, &mapQ_d, &same_d);
@@ -2077,7 +2083,10 @@ static int sens_launch(qpg_batch *bt, qpg_adjoint_args &ar, bool maps, const Sub
   ar.list = sub.list;
   const int grid = std::min(sub.count(bt), bt->nslots);
   const size_t shm = (size_t)bt->lds_bytes;
-  if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
+  if (K > 1) { /* (K = 1: the single calls' kernel, whichever entry point the call came through) */
+    if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint_multi<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
+    else BT_LAUNCH(bt, k_adjoint_multi<1>, grid, shm, bt->V, ar);
+  } else if (bt->sparse) RT_LAUNCH(QP_INST(qp512, k_adjoint<QPG_RPT_SPARSE>), grid, QP_T, shm, bt->V, ar);
   else BT_LAUNCH(bt, k_adjoint<1>, grid, shm, bt->V, ar);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_adjoint failed: " + std::string(RT_LAST_ERROR()));
   return api_ok();
@@ -2102,8 +2111,9 @@ static int sens_point(const std::string &fn, bool use_at, const QPGDevicePoint *
   return QPG_OK;
 }
 static int adjoint_run(qpg_batch *bt, const std::string &fn, const QPGDeviceAdjoint *io, bool use_at, const QPGDevicePoint *at, const qpg_int *d_select,
-                       qpg_int *n_selected) {
+                       qpg_int *n_selected, qpg_int K = 1) {
   NEED_SETUP(bt, fn);
+  if (K < 1 || K > 0x7fffffff) return fail(QPG_ERR_INVALID, fn + ": K must be at least 1");
   if (!io || !io->gx) return fail(QPG_ERR_INVALID, fn + ": gx is NULL");
   const qpg_int *active_in;
   { const int rc = sens_point(fn, use_at, at, io->active_in, &active_in); if (rc != QPG_OK) return rc; }
@@ -2116,7 +2126,7 @@ static int adjoint_run(qpg_batch *bt, const std::string &fn, const QPGDeviceAdjo
   if (use_at) { ar.at_x = at->x; ar.at_y = at->y; }
   ar.dq = io->dq; ar.dbmin = io->dbmin; ar.dbmax = io->dbmax; ar.dQx = io->dQx; ar.dAx = io->dAx;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
-  return sens_launch(bt, ar, io->dQx || io->dAx, sub);
+  return sens_launch(bt, ar, io->dQx || io->dAx, sub, K);
 }
 extern "C" int qpg_batch_adjoint_device(qpg_batch *bt, const QPGDeviceAdjoint *io) { return qpg_batch_adjoint_subset_device(bt, io, nullptr, nullptr); }
 extern "C" int qpg_batch_adjoint_subset_device(qpg_batch *bt, const QPGDeviceAdjoint *io, const qpg_int *d_select, qpg_int *n_selected) {
@@ -2128,8 +2138,9 @@ extern "C" int qpg_batch_adjoint_at_device(qpg_batch *bt, const QPGDeviceAdjoint
 /* The tangent of the solved batch (include/qpalm_gfx950.h; DESIGN.md section 13): the adjoint's launch in its other mode -- the same kernel, set-up,
  * factor and refinement, on the right-hand side of a direction. */
 static int tangent_run(qpg_batch *bt, const std::string &fn, const QPGDeviceTangent *io, bool use_at, const QPGDevicePoint *at, const qpg_int *d_select,
-                       qpg_int *n_selected) {
+                       qpg_int *n_selected, qpg_int K = 1) {
   NEED_SETUP(bt, fn);
+  if (K < 1 || K > 0x7fffffff) return fail(QPG_ERR_INVALID, fn + ": K must be at least 1");
   if (!io || (!io->dq && !io->dbmin && !io->dbmax && !io->dQx && !io->dAx)) return fail(QPG_ERR_INVALID, fn + ": no direction (dq, dbmin, dbmax, dQx and dAx are all NULL)");
   const qpg_int *active_in;
   { const int rc = sens_point(fn, use_at, at, io->active_in, &active_in); if (rc != QPG_OK) return rc; }
@@ -2143,7 +2154,7 @@ static int tangent_run(qpg_batch *bt, const std::string &fn, const QPGDeviceTang
   ar.t_dq = io->dq; ar.t_dbmin = io->dbmin; ar.t_dbmax = io->dbmax; ar.t_dQx = io->dQx; ar.t_dAx = io->dAx;
   ar.dx = io->dx; ar.dy = io->dy;
   ar.active_out = (int64_t *)io->active_out; ar.flag = (int64_t *)io->flag; ar.passes = (int64_t *)io->passes; ar.resid = io->resid;
-  return sens_launch(bt, ar, io->dQx || io->dAx, sub);
+  return sens_launch(bt, ar, io->dQx || io->dAx, sub, K);
 }
 extern "C" int qpg_batch_tangent_device(qpg_batch *bt, const QPGDeviceTangent *io) { return qpg_batch_tangent_subset_device(bt, io, nullptr, nullptr); }
 extern "C" int qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTangent *io, const qpg_int *d_select, qpg_int *n_selected) {
@@ -2151,6 +2162,17 @@ extern "C" int qpg_batch_tangent_subset_device(qpg_batch *bt, const QPGDeviceTan
 }
 extern "C" int qpg_batch_tangent_at_device(qpg_batch *bt, const QPGDeviceTangent *io, const QPGDevicePoint *at, const qpg_int *d_select, qpg_int *n_selected) {
   return tangent_run(bt, "qpg_batch_tangent_at_device", io, true, at, d_select, n_selected);
+}
+/* K directions per call (include/qpalm_gfx950.h; DESIGN.md section 18): the same runners -- one round trip for in_solve, one k_adjoint_check, one selection
+ * and one launch, in which a member's directions run one after another on the factor its set-up left.  at / d_select = NULL: the stored solutions / every
+ * member, so one entry point covers the plain, the subset and the recorded-point forms. */
+extern "C" int qpg_batch_adjoint_multi_device(qpg_batch *bt, const QPGDeviceAdjoint *io, qpg_int K, const QPGDevicePoint *at, const qpg_int *d_select,
+                                              qpg_int *n_selected) {
+  return adjoint_run(bt, "qpg_batch_adjoint_multi_device", io, at != nullptr, at, d_select, n_selected, K);
+}
+extern "C" int qpg_batch_tangent_multi_device(qpg_batch *bt, const QPGDeviceTangent *io, qpg_int K, const QPGDevicePoint *at, const qpg_int *d_select,
+                                              qpg_int *n_selected) {
+  return tangent_run(bt, "qpg_batch_tangent_multi_device", io, at != nullptr, at, d_select, n_selected, K);
 }
 /* The active set of the stored solutions on its own (include/qpalm_gfx950.h; k_get_active): what active_out of an adjoint call on this state holds */
 extern "C" int qpg_batch_get_active_device(qpg_batch *bt, qpg_int *d_active) { return qpg_batch_get_active_subset_device(bt, d_active, nullptr, nullptr); }

@@ -188,6 +188,12 @@ typedef struct {
   /* at_x != NULL: the call is qpg_batch_adjoint_at_device / qpg_batch_tangent_at_device (QPGDevicePoint): the point is the caller's [B][n] / [B][m] arrays
    * instead of the stored solutions, active_in (required then) is its active set, and the members' statuses are not consulted */
   const double *at_x, *at_y;
+  /* ndir >= 1 directions per member (qpg_batch_adjoint_multi_device / qpg_batch_tangent_multi_device): direction k reads and writes
+   * every per-direction array k * dir_* elements further on -- dir_n for the [B][n] arrays (gx, dq, t_dq, dx), dir_m for the [B][m] ones (gy, dbmin,
+   * dbmax, t_dbmin, t_dbmax, dy), dir_Q / dir_A for the [B][strideQ] / [B][strideA] ones, dir_b for flag, resid and passes.  active_in, active_out,
+   * at_x / at_y and list are shared by the directions.  The single calls: ndir = 1 and all five 0.  The polish has one direction. */
+  int32_t ndir;
+  int64_t dir_n, dir_m, dir_Q, dir_A, dir_b;
 } qpg_adjoint_args;
 
 #define QPG_RPT_SPARSE 8 /* template argument of k_solve / dev_solve that selects the sparse factor (the dense instances use 0, 1, 2, 4) */

@@ -473,6 +473,131 @@ class QpalmBatch:
             out["n_selected"] = cnt
         return out
 
+    # -- K directions per call ---------------------------------------------------
+    def _leading(self, what, K, *arrays):
+        """K of a multi call: the leading dimension of the first tensor among `arrays`, which the others must share (their full shapes are checked
+        by _dev_args); `K` itself when it is given, which raw addresses need"""
+        for v in arrays:
+            if hasattr(v, "data_ptr"):
+                if v.dim() < 1:
+                    raise ValueError("%s: expected a leading dimension K on every per-direction tensor" % what)
+                k = int(v.shape[0])
+                if K is not None and int(K) != k:
+                    raise ValueError("%s: K = %d, but a tensor has the leading dimension %d" % (what, int(K), k))
+                K = k
+                break
+        if K is None:
+            raise ValueError("%s: K cannot be taken from raw addresses, pass K" % what)
+        return int(K)
+
+    def _multi_call(self, name, io, K, select, at):
+        """qpg_batch_<name>_multi_device: select and at as for _sens_call, both optional; returns (rc, n_selected)"""
+        if at is not None and (not isinstance(at, (tuple, list)) or len(at) != 3 or any(v is None for v in at)):
+            raise ValueError("at: expected (x, y, active), all three given")
+        if select is not None and (isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr")):
+            raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
+        x, y, act = at if at is not None else (None, None, None)
+        x, y, act, sel = self._dev_args((x, (self.B, self.n), "at x", "float64"), (y, (self.B, self.m), "at y", "float64"),
+                                        (act, (self.B, self.m), "at active", "int64"), (select, (self.B,), "select", "int64"))
+        point = C.byref(capi.DevicePoint(x, y, act)) if at is not None else None
+        cnt = capi.c_int(0)
+        rc = getattr(self.L, "qpg_batch_%s_multi_device" % name)(self.h, C.byref(io), K, point, sel, C.byref(cnt))
+        return rc, int(cnt.value)
+
+    def adjoints_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None, at=None, K=None):
+        """adjoint_device for K pairs (gx, gy) in one call (qpg_batch_adjoint_multi_device, DESIGN.md section 18): gx [K][B][n], gy [K][B][m] or None;
+        the outputs dq, dbmin, dbmax, dQx, dAx, flag, resid and passes have the same leading K, `active` (input and output, [B][m]), select and at are
+        those of adjoint_device and shared by the directions.  K is the leading dimension of gx (pass K when gx is a raw address).  Slice k of every
+        output holds the bits adjoint_device returns for slice k of the inputs; the set-up, the factor and the host's checks are paid once.  A
+        direction that fails is flagged in its own slice; a member that is not solved is flagged in all of them.  `epoch` stays."""
+        nB, n, m = self.B, self.n, self.m
+        if gx is None:
+            raise ValueError("gx: expected a torch tensor or a raw address")
+        K = self._leading("adjoints_device", K, gx, gy)
+        shapes = dict(dq=((K, nB, n), "float64"), dbmin=((K, nB, m), "float64"), dbmax=((K, nB, m), "float64"), dQx=((K, nB, self.nnzQ), "float64"),
+                      dAx=((K, nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((K, nB), "int64"), resid=((K, nB), "float64"),
+                      passes=((K, nB), "int64"))
+        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
+        if unknown:
+            raise ValueError("adjoints_device: unknown outputs %r" % sorted(unknown))
+        if out is None:
+            out = {k: self._empty(*shapes[k]) for k in want}
+        a = self._dev_args((gx, (K, nB, n), "gx", "float64"), (gy, (K, nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
+                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
+        rc, cnt = self._multi_call("adjoint", capi.DeviceAdjoint(*a), K, select, at)
+        self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
+        return out
+
+    def tangents_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None, at=None,
+                        K=None):
+        """tangent_device for K directions in one call (qpg_batch_tangent_multi_device): dq [K][B][n], dbmin / dbmax [K][B][m],
+        dQx [K][B][nnzQ_max], dAx [K][B][nnzA_max]; None = zero in every direction, at least one must be given.  The outputs dx, dy, flag, resid and
+        passes have the same leading K; `active` (input and output, [B][m]), select and at are those of tangent_device and shared by the directions.
+        K is the leading dimension of the first tensor given (pass K with raw addresses).  Slice k of every output holds the bits tangent_device
+        returns for slice k of the inputs.  `epoch` stays."""
+        nB, n, m = self.B, self.n, self.m
+        dirs = (dq, dbmin, dbmax, dQx, dAx)
+        if all(v is None for v in dirs):
+            raise ValueError("tangents_device: no direction (dq, dbmin, dbmax, dQx and dAx are all None)")
+        K = self._leading("tangents_device", K, *dirs)
+        shapes = dict(dx=((K, nB, n), "float64"), dy=((K, nB, m), "float64"), active=((nB, m), "int64"), flag=((K, nB), "int64"),
+                      resid=((K, nB), "float64"), passes=((K, nB), "int64"))
+        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
+        if unknown:
+            raise ValueError("tangents_device: unknown outputs %r" % sorted(unknown))
+        if out is None:
+            out = {k: self._empty(*shapes[k]) for k in want}
+        a = self._dev_args((dq, (K, nB, n), "dq", "float64"), (dbmin, (K, nB, m), "dbmin", "float64"), (dbmax, (K, nB, m), "dbmax", "float64"),
+                           (dQx, (K, nB, self.nnzQ), "dQx", "float64"), (dAx, (K, nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
+                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
+        rc, cnt = self._multi_call("tangent", capi.DeviceTangent(*a), K, select, at)
+        self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
+        return out
+
+    def jacobian_device(self, wrt="q", mode="tangent", chunk=16, active=None, select=None, at=None):
+        """The Jacobian of the stored solutions with respect to q, bmin or bmax, column block by column block through the multi calls: a dict with
+        dx [B][n][p], dy [B][m][p] (mode "tangent" only) and flag [B] (the largest flag over the directions), p = n for wrt "q" and m for "bmin" /
+        "bmax".  mode "tangent": the directions are the unit vectors of the chosen input, at most `chunk` per call (p / chunk calls, the last one
+        shorter).  mode "adjoint": the seeds are the unit vectors of x (gx = e_j, gy = None), and row j of dx is the dq / dbmin / dbmax of seed j --
+        n solves instead of p.  A unit vector beyond a sized member's own n / m gives a zero column (row): the engine ignores such entries.  active,
+        select and at: as for tangent_device; the rows of members that are not selected are zeros.  `epoch` stays."""
+        import torch
+        if wrt not in ("q", "bmin", "bmax"):
+            raise ValueError("jacobian_device: wrt is 'q', 'bmin' or 'bmax'")
+        if mode not in ("tangent", "adjoint"):
+            raise ValueError("jacobian_device: mode is 'tangent' or 'adjoint'")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("jacobian_device: chunk must be at least 1")
+        nB, n, m = self.B, self.n, self.m
+        p = n if wrt == "q" else m
+        res = dict(dx=self._empty((nB, n, p)).zero_(), flag=self._empty((nB,), "int64").zero_())
+        if mode == "tangent":
+            res["dy"] = self._empty((nB, m, p)).zero_()
+        ndirs = p if mode == "tangent" else n   # tangent: unit vectors of the input; adjoint: unit vectors of x
+        name = "d" + wrt
+        for j0 in range(0, ndirs, chunk):
+            kc = min(chunk, ndirs - j0)
+            seed = self._empty((kc, nB, ndirs)).zero_()
+            for k in range(kc):
+                seed[k, :, j0 + k] = 1.0
+            flag = self._empty((kc, nB), "int64").zero_()
+            if mode == "tangent":
+                out = dict(dx=self._empty((kc, nB, n)).zero_(), dy=self._empty((kc, nB, m)).zero_(), flag=flag)
+                self.tangents_device(**{name: seed}, active=active, out=out, select=select, at=at)
+                res["dx"][:, :, j0:j0 + kc] = out["dx"].permute(1, 2, 0)
+                res["dy"][:, :, j0:j0 + kc] = out["dy"].permute(1, 2, 0)
+            else:
+                out = {name: self._empty((kc, nB, p)).zero_(), "flag": flag}
+                self.adjoints_device(seed, active=active, out=out, select=select, at=at)
+                res["dx"][:, j0:j0 + kc, :] = out[name].permute(1, 0, 2)
+            res["flag"] = torch.maximum(res["flag"], flag.max(dim=0).values)
+        return res
+
     @property
     def sens_penalty(self):
         """The penalty floor of adjoint_device, tangent_device and polish_device (qpg_batch_set_sens_penalty): the preconditioner of
