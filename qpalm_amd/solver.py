@@ -5,7 +5,10 @@ qpalm_setup / _solve / _warm_start / _update_bounds / _update_q) for ONE QP; `Qp
 batched form the MI355X engine is built for (B independent QPs of equal dimensions resident in HBM).
 Neither class contains numerics: everything runs in the HIP kernels behind include/qpalm_gfx950.h.
 """
+import collections
 import ctypes as C
+import time
+import weakref
 
 import numpy as np
 
@@ -20,18 +23,18 @@ class Context:
     def __init__(self, device=0, lib_path=None, **options):
         self.L = capi.load(lib_path)
         h = C.c_void_p()
-        rc = self.L.qpg_ctx_create(int(device), C.byref(h))
-        if rc != 0:
-            raise QpgError(rc, self.L.qpg_last_error().decode())
+        self._check(self.L.qpg_ctx_create(int(device), C.byref(h)))
         self.h = h
         self.device = int(device)
         for k, v in options.items():
             self.set_option(k, v)
 
-    def set_option(self, name, value):
-        rc = self.L.qpg_ctx_set_option(self.h, name.encode(), int(value))
+    def _check(self, rc):
         if rc != 0:
             raise QpgError(rc, self.L.qpg_last_error().decode())
+
+    def set_option(self, name, value):
+        self._check(self.L.qpg_ctx_set_option(self.h, name.encode(), int(value)))
 
     @property
     def backend(self):
@@ -49,9 +52,7 @@ class Context:
     def hbm_copy_gbs(self, nbytes=1 << 30, reps=5):
         """measured copy bandwidth of the device (GB/s, read + write): the attainable-HBM yardstick of bench.py"""
         g = C.c_float(0.0)
-        rc = self.L.qpg_ctx_hbm_copy_gbs(self.h, int(nbytes), int(reps), C.byref(g))
-        if rc != 0:
-            raise QpgError(rc, self.L.qpg_last_error().decode())
+        self._check(self.L.qpg_ctx_hbm_copy_gbs(self.h, int(nbytes), int(reps), C.byref(g)))
         return float(g.value)
 
     def pinned_array(self, shape):
@@ -60,28 +61,52 @@ class Context:
         shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         count = int(np.prod(shape)) if shape else 1
         p = C.c_void_p()
-        rc = self.L.qpg_host_alloc(self.h, max(count, 1) * 8, C.byref(p))
-        if rc != 0:
-            raise QpgError(rc, self.L.qpg_last_error().decode())
+        self._check(self.L.qpg_host_alloc(self.h, max(count, 1) * 8, C.byref(p)))
         buf = (C.c_double * max(count, 1)).from_address(p.value)
         arr = np.frombuffer(buf, dtype=np.float64, count=count).reshape(shape)
         ctx_l, ctx_h, addr = self.L, self.h, p.value
-        import weakref
         weakref.finalize(buf, lambda: ctx_l.qpg_host_free(ctx_h, C.c_void_p(addr)))
         return arr
 
     def hbm_read_gbs(self, nbytes=1 << 30, reps=5):
         """measured read-only streaming bandwidth of the device (GB/s)"""
         g = C.c_float(0.0)
-        rc = self.L.qpg_ctx_hbm_read_gbs(self.h, int(nbytes), int(reps), C.byref(g))
-        if rc != 0:
-            raise QpgError(rc, self.L.qpg_last_error().decode())
+        self._check(self.L.qpg_ctx_hbm_read_gbs(self.h, int(nbytes), int(reps), C.byref(g)))
         return float(g.value)
 
     def close(self):
         if self.h:
             self.L.qpg_ctx_destroy(self.h)
             self.h = None
+
+
+# The arrays of the per-step device calls, one row each, in the field order of the call's struct (capi.Device*; DeviceStep.warm and DevicePolish.store
+# are values, not arrays).  key: an input's name in error messages, an output's key in `want` / `out`.  width: an attribute of the batch (n, m, nnzQ,
+# nnzA), 1 (a scalar per member) or 4.  per_dir: the array gains the leading K of adjoints_device / tangents_device; `active` (in and out) does not.
+_Row = collections.namedtuple("_Row", "field key width dtype out per_dir")
+
+
+def _in(field, width, dtype="float64", per_dir=False, key=None):
+    return _Row(field, key or field, width, dtype, False, per_dir)
+
+
+def _out(key, width, dtype="float64", per_dir=False):
+    return _Row("active_out" if key == "active" else key, key, width, dtype, True, per_dir)
+
+
+_SENS_OUT = (_out("active", "m", "int64"), _out("flag", 1, "int64", True), _out("resid", 1, per_dir=True), _out("passes", 1, "int64", True))
+_CALLS = dict(
+    step=(capi.DeviceStep, (_in("bmin", "m"), _in("bmax", "m"), _in("q", "n"), _in("warm_x", "n", key="warm x"), _in("warm_y", "m", key="warm y"),
+                            _out("x", "n"), _out("y", "m"), _out("status_val", 1, "int64"), _out("iter", 1, "int64"), _out("rejected", 1, "int64"))),
+    adjoint=(capi.DeviceAdjoint, (_in("gx", "n", per_dir=True), _in("gy", "m", per_dir=True), _in("active_in", "m", "int64", key="active"),
+                                  _out("dq", "n", per_dir=True), _out("dbmin", "m", per_dir=True), _out("dbmax", "m", per_dir=True),
+                                  _out("dQx", "nnzQ", per_dir=True), _out("dAx", "nnzA", per_dir=True)) + _SENS_OUT),
+    tangent=(capi.DeviceTangent, (_in("dq", "n", per_dir=True), _in("dbmin", "m", per_dir=True), _in("dbmax", "m", per_dir=True),
+                                  _in("dQx", "nnzQ", per_dir=True), _in("dAx", "nnzA", per_dir=True), _in("active_in", "m", "int64", key="active"),
+                                  _out("dx", "n", per_dir=True), _out("dy", "m", per_dir=True)) + _SENS_OUT),
+    polish=(capi.DevicePolish, (_in("active_in", "m", "int64"), _out("x", "n"), _out("y", "m"), _out("res", 4)) + _SENS_OUT))
+for _struct, _arrays in _CALLS.values():   # the rows are the struct's arrays, in its order: _io fills the struct by position
+    assert [r.field for r in _arrays] == [f for f, kind in _struct._fields_ if kind is C.c_void_p], _struct
 
 
 class QpalmBatch:
@@ -101,8 +126,9 @@ class QpalmBatch:
         # counts the calls that change the values of Q and A (a setup, update_Q_A*): a point recorded under another count is no longer valid for
         # adjoint_device / tangent_device(at=...)
         self.matrix_epoch = 1
+        self._row_cache = {}   # _rows
+        self._emulated = ctx.backend == "host-emulation"   # device memory is host memory there; asked once: the per-step calls check every array
         h = C.c_void_p()
-        import time
         t0 = time.perf_counter()
         self._check(self.L.qpg_batch_create(ctx.h, self.B, self.n, self.m, nnzA, nnzQ, C.byref(self.settings), C.byref(h)))
         self.h = h
@@ -263,7 +289,7 @@ class QpalmBatch:
             raise ValueError("%s: expected a torch tensor or a raw address, got %s" % (what, type(v).__name__))
         import torch
         want = getattr(torch, dtype)
-        on_gpu = self.ctx.backend != "host-emulation"
+        on_gpu = not self._emulated
         if v.device.type != ("cuda" if on_gpu else "cpu") or (on_gpu and v.device.index != self.ctx.device):
             raise ValueError("%s: tensor on %s, the batch lives on %s" % (what, v.device, "cuda:%d" % self.ctx.device if on_gpu else "cpu (emulation)"))
         if v.dtype != want:
@@ -278,14 +304,14 @@ class QpalmBatch:
         """addresses (c_void_p or None) of several arrays, all checked first; then, if any was a tensor, torch's current stream on the device is
         synchronised -- the calls are synchronous: whatever produced the inputs must have finished"""
         got = [self._dev(v, shape, what, dtype) for v, shape, what, dtype in specs]
-        if any(t for _, t in got) and self.ctx.backend != "host-emulation":
+        if any(t for _, t in got) and not self._emulated:
             import torch
             torch.cuda.current_stream(self.ctx.device).synchronize()
         return [C.c_void_p(a) if a is not None else None for a, _ in got]
 
     def _empty(self, shape, dtype="float64"):
         import torch
-        dev = "cpu" if self.ctx.backend == "host-emulation" else "cuda:%d" % self.ctx.device
+        dev = "cpu" if self._emulated else "cuda:%d" % self.ctx.device
         return torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
 
     def update_bounds_device(self, bmin=None, bmax=None):
@@ -320,32 +346,73 @@ class QpalmBatch:
         self._check(self.L.qpg_batch_get_status_device(self.h, a, b))
         return sv, it
 
-    STEP_OUT = ("x", "y", "status_val", "iter", "rejected")
+    STEP_OUT, ADJOINT_OUT, TANGENT_OUT, POLISH_OUT = (tuple(r.key for r in _CALLS[c][1] if r.out) for c in ("step", "adjoint", "tangent", "polish"))
 
-    def _subset_call(self, name, io, select):
-        """the full call (select is None), or its subset form with select ([B] int64 tensor on the batch's device, entries 0 / 1, validated like every
-        other array); returns (rc, n_selected)"""
-        if select is None:
-            return getattr(self.L, "qpg_batch_%s_device" % name)(self.h, C.byref(io)), self.B
-        if isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr"):
-            raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
-        sel, = self._dev_args((select, (self.B,), "select", "int64"))
-        cnt = capi.c_int(0)
-        rc = getattr(self.L, "qpg_batch_%s_subset_device" % name)(self.h, C.byref(io), sel, C.byref(cnt))
-        return rc, int(cnt.value)
+    def _rows(self, call, K=None):
+        """(inputs, outputs, value fields) of a device call of _CALLS in this batch: [(shape, name, dtype)] of its input arrays in struct order, as
+        _dev_args takes them, {key: (shape, name, dtype)} of its outputs likewise, and the positions in the struct of the fields that are not arrays.
+        The per-direction arrays have the leading K of a plural call.  Worked out once per (call, K): the calls are made every step."""
+        got = self._row_cache.get((call, K))
+        if got is None:
+            def spec(r):
+                shape = (self.B,) if r.width == 1 else (self.B, r.width if isinstance(r.width, int) else getattr(self, r.width))
+                return ((K,) + shape if K is not None and r.per_dir else shape), ("out " + r.key if r.out else r.key), r.dtype
+            struct, rows = _CALLS[call]
+            values = [i for i, (_, kind) in enumerate(struct._fields_) if kind is not C.c_void_p]
+            got = self._row_cache[call, K] = [spec(r) for r in rows if not r.out], {r.key: spec(r) for r in rows if r.out}, values
+        return got
 
-    def _sens_call(self, name, io, select, at):
-        """_subset_call, or with at = (x, y, active) the call at a recorded point (qpg_batch_<name>_at_device, which takes select itself)"""
-        if at is None:
-            return self._subset_call(name, io, select)
-        if not isinstance(at, (tuple, list)) or len(at) != 3 or any(v is None for v in at):
-            raise ValueError("at: expected (x, y, active), all three given")
+    def _outputs(self, call, want, out, K, err):
+        """(out, specs) of a device call: the dict of its outputs -- `out` itself, or new tensors for the keys in `want` -- and the _dev_args specs of
+        all its outputs in struct order (a key that is absent or None: not wanted).  A key the call does not have: ValueError(err ...)"""
+        rows = self._rows(call, K)[1]
+        unknown = set(out if out is not None else want) - set(rows) - {"n_selected"}
+        if unknown:
+            raise ValueError("%s %r" % (err, sorted(unknown)))
+        if out is None:
+            out = {k: self._empty(rows[k][0], rows[k][2]) for k in want}
+        return out, [(out.get(k),) + spec for k, spec in rows.items()]
+
+    def _zeros(self, call, keys, K=None):
+        """zero-filled tensors for these outputs of a device call: an `out` whose rows stay zero where the call writes nothing"""
+        rows = self._rows(call, K)[1]
+        return {k: self._empty(rows[k][0], rows[k][2]).zero_() for k in keys}
+
+    def _io(self, call, ins, specs, K=None, value=None):
+        """the struct of a device call: its input arrays `ins` in struct order and its outputs' `specs`, all checked by _dev_args; `value`: its field
+        that is not an array"""
+        rows, _, values = self._rows(call, K)
+        fields = self._dev_args(*[(v,) + spec for v, spec in zip(ins, rows)], *specs)
+        for i in values:
+            fields.insert(i, value)
+        return _CALLS[call][0](*fields)
+
+    def _check_select(self, select):
         if select is not None and (isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr")):
             raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
-        x, y, act, sel = self._dev_args((at[0], (self.B, self.n), "at x", "float64"), (at[1], (self.B, self.m), "at y", "float64"),
-                                        (at[2], (self.B, self.m), "at active", "int64"), (select, (self.B,), "select", "int64"))
+
+    def _route(self, name, io, select=None, at=None, K=None):
+        """The entry point of a form of a device call; returns (rc, n_selected).  Nothing given: qpg_batch_<name>_device.  select ([B] int64 tensor on the
+        batch's device, entries 0 / 1, validated like every other array): qpg_batch_<name>_subset_device.  at = (x, y, active), a recorded point:
+        qpg_batch_<name>_at_device, which takes select itself.  K (the plural methods; None otherwise): qpg_batch_<name>_multi_device, select and at
+        both optional."""
+        fn = "qpg_batch_%s_" % name
+        if select is None and at is None and K is None:
+            return getattr(self.L, fn + "device")(self.h, C.byref(io)), self.B
+        if at is not None and (not isinstance(at, (tuple, list)) or len(at) != 3 or any(v is None for v in at)):
+            raise ValueError("at: expected (x, y, active), all three given")
+        self._check_select(select)
+        x, y, act = at if at is not None else (None, None, None)
+        x, y, act, sel = self._dev_args((x, (self.B, self.n), "at x", "float64"), (y, (self.B, self.m), "at y", "float64"),
+                                        (act, (self.B, self.m), "at active", "int64"), (select, (self.B,), "select", "int64"))
+        point = C.byref(capi.DevicePoint(x, y, act)) if at is not None else None
         cnt = capi.c_int(0)
-        rc = getattr(self.L, "qpg_batch_%s_at_device" % name)(self.h, C.byref(io), C.byref(capi.DevicePoint(x, y, act)), sel, C.byref(cnt))
+        if K is not None:
+            rc = getattr(self.L, fn + "multi_device")(self.h, C.byref(io), K, point, sel, C.byref(cnt))
+        elif at is not None:
+            rc = getattr(self.L, fn + "at_device")(self.h, C.byref(io), point, sel, C.byref(cnt))
+        else:
+            rc = getattr(self.L, fn + "subset_device")(self.h, C.byref(io), sel, C.byref(cnt))
         return rc, int(cnt.value)
 
     def active_device(self, out=None, select=None):
@@ -361,8 +428,7 @@ class QpalmBatch:
         if select is None:
             self._check(self.L.qpg_batch_get_active_device(self.h, a))
         else:
-            if isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr"):
-                raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
+            self._check_select(select)
             sel, = self._dev_args((select, (self.B,), "select", "int64"))
             self._check(self.L.qpg_batch_get_active_subset_device(self.h, a, sel, None))
         return out
@@ -378,12 +444,7 @@ class QpalmBatch:
         allocated here hold uninitialised memory there).  With select the returned dict also holds n_selected (an int: how many members took the
         step; the key is ignored when the dict is handed in again); an entry other than 0 / 1, or a solve in progress, raises QpgError (-2)."""
         self.epoch += 1
-        if out is None:
-            out = dict(x=self._empty((self.B, self.n)), y=self._empty((self.B, self.m)), status_val=self._empty((self.B,), "int64"),
-                       iter=self._empty((self.B,), "int64"), rejected=self._empty((self.B,), "int64"))
-        unknown = set(out) - set(self.STEP_OUT) - {"n_selected"}
-        if unknown:
-            raise ValueError("out: unknown keys %r" % sorted(unknown))
+        out, specs = self._outputs("step", self.STEP_OUT, out, None, "out: unknown keys")
         if warm is None:
             mode, wx, wy = 0, None, None
         elif isinstance(warm, str):
@@ -395,21 +456,33 @@ class QpalmBatch:
             wx, wy = warm
             if wx is None and wy is None:
                 raise ValueError("warm: (x, y) with both None")
-        nB, n, m = self.B, self.n, self.m
-        a = self._dev_args((bmin, (nB, m), "bmin", "float64"), (bmax, (nB, m), "bmax", "float64"), (q, (nB, n), "q", "float64"),
-                           (wx, (nB, n), "warm x", "float64"), (wy, (nB, m), "warm y", "float64"),
-                           (out.get("x"), (nB, n), "out x", "float64"), (out.get("y"), (nB, m), "out y", "float64"),
-                           (out.get("status_val"), (nB,), "out status_val", "int64"), (out.get("iter"), (nB,), "out iter", "int64"),
-                           (out.get("rejected"), (nB,), "out rejected", "int64"))
-        io = capi.DeviceStep(a[0], a[1], a[2], a[3], a[4], mode, a[5], a[6], a[7], a[8], a[9])
-        rc, cnt = self._subset_call("step", io, select)
+        rc, cnt = self._route("step", self._io("step", (bmin, bmax, q, wx, wy), specs, value=mode), select)
         if rc not in (0, -2) or (rc == -2 and select is not None and b"Lower bound" not in self.L.qpg_last_error()):
             self._check(rc)
         if select is not None:
             out["n_selected"] = cnt
         return rc, out
 
-    ADJOINT_OUT = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
+    def _sens(self, name, dirs, active, want, out, select, at, plural=False, K=None):
+        """the body of adjoint_device / adjoints_device (name "adjoint", dirs = (gx, gy)) and of tangent_device / tangents_device (name "tangent",
+        dirs = (dq, dbmin, dbmax, dQx, dAx))"""
+        method = name + ("s_device" if plural else "_device")
+        if name == "adjoint":
+            missing = "gx: expected a torch tensor or a raw address" if dirs[0] is None else None
+        else:
+            missing = "%s: no direction (dq, dbmin, dbmax, dQx and dAx are all None)" % method if all(v is None for v in dirs) else None
+        if plural:   # K comes first: the outputs' shapes need it
+            if missing:
+                raise ValueError(missing)
+            K = self._leading(method, K, *dirs)
+        out, specs = self._outputs(name, want, out, K, method + ": unknown outputs")
+        if missing:
+            raise ValueError(missing)
+        rc, cnt = self._route(name, self._io(name, dirs + (active,), specs, K), select, at, K)
+        self._check(rc)
+        if select is not None:
+            out["n_selected"] = cnt
+        return out
 
     def adjoint_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None, at=None):
         """Gradients of a loss through the stored solutions (qpg_batch_adjoint_device): gx = dl/dx [B][n], gy = dl/dy [B][m] or None, active = the active
@@ -423,27 +496,7 @@ class QpalmBatch:
         of a sensitivity call made then): the gradients are those of THAT solve (qpg_batch_adjoint_at_device), however often the
         batch has been stepped since.  Valid while `matrix_epoch` is what it was at that solve; q, bounds, penalties and warm starts may differ.  The
         members' current statuses are not consulted (no flag 2): exclude members with select.  `active` must be None then."""
-        nB, n, m = self.B, self.n, self.m
-        shapes = dict(dq=((nB, n), "float64"), dbmin=((nB, m), "float64"), dbmax=((nB, m), "float64"), dQx=((nB, self.nnzQ), "float64"),
-                      dAx=((nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
-                      passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
-        if unknown:
-            raise ValueError("adjoint_device: unknown outputs %r" % sorted(unknown))
-        if gx is None:
-            raise ValueError("gx: expected a torch tensor or a raw address")
-        if out is None:
-            out = {k: self._empty(*shapes[k]) for k in want}
-        a = self._dev_args((gx, (nB, n), "gx", "float64"), (gy, (nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
-                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
-        io = capi.DeviceAdjoint(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11])
-        rc, cnt = self._sens_call("adjoint", io, select, at)
-        self._check(rc)
-        if select is not None:
-            out["n_selected"] = cnt
-        return out
-
-    TANGENT_OUT = ("dx", "dy", "active", "flag", "resid", "passes")
+        return self._sens("adjoint", (gx, gy), active, want, out, select, at)
 
     def tangent_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None, at=None):
         """How the stored solutions move along one direction of the data (qpg_batch_tangent_device): dq [B][n], dbmin / dbmax [B][m], dQx [B][nnzQ_max],
@@ -453,25 +506,7 @@ class QpalmBatch:
         to fill instead (then `want` is ignored).  Returns the dict.  The batch's state (and `epoch`) stays: x + dx, y + dy is a first-order
         prediction of the next solution and can go straight into warm_start_device.  select: as for adjoint_device
         (qpg_batch_tangent_subset_device).  at: as for adjoint_device (qpg_batch_tangent_at_device)."""
-        nB, n, m = self.B, self.n, self.m
-        shapes = dict(dx=((nB, n), "float64"), dy=((nB, m), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"), resid=((nB,), "float64"),
-                      passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
-        if unknown:
-            raise ValueError("tangent_device: unknown outputs %r" % sorted(unknown))
-        if all(v is None for v in (dq, dbmin, dbmax, dQx, dAx)):
-            raise ValueError("tangent_device: no direction (dq, dbmin, dbmax, dQx and dAx are all None)")
-        if out is None:
-            out = {k: self._empty(*shapes[k]) for k in want}
-        a = self._dev_args((dq, (nB, n), "dq", "float64"), (dbmin, (nB, m), "dbmin", "float64"), (dbmax, (nB, m), "dbmax", "float64"),
-                           (dQx, (nB, self.nnzQ), "dQx", "float64"), (dAx, (nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
-                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
-        io = capi.DeviceTangent(*a)
-        rc, cnt = self._sens_call("tangent", io, select, at)
-        self._check(rc)
-        if select is not None:
-            out["n_selected"] = cnt
-        return out
+        return self._sens("tangent", (dq, dbmin, dbmax, dQx, dAx), active, want, out, select, at)
 
     # -- K directions per call (DESIGN.md section 18) ---------------------------------------------------
     def _leading(self, what, K, *arrays):
@@ -490,45 +525,13 @@ class QpalmBatch:
             raise ValueError("%s: K cannot be taken from raw addresses, pass K" % what)
         return int(K)
 
-    def _multi_call(self, name, io, K, select, at):
-        """qpg_batch_<name>_multi_device: select and at as for _sens_call, both optional; returns (rc, n_selected)"""
-        if at is not None and (not isinstance(at, (tuple, list)) or len(at) != 3 or any(v is None for v in at)):
-            raise ValueError("at: expected (x, y, active), all three given")
-        if select is not None and (isinstance(select, (int, np.integer)) or not hasattr(select, "data_ptr")):
-            raise ValueError("select: expected an int64 torch tensor of shape (%d,)" % self.B)
-        x, y, act = at if at is not None else (None, None, None)
-        x, y, act, sel = self._dev_args((x, (self.B, self.n), "at x", "float64"), (y, (self.B, self.m), "at y", "float64"),
-                                        (act, (self.B, self.m), "at active", "int64"), (select, (self.B,), "select", "int64"))
-        point = C.byref(capi.DevicePoint(x, y, act)) if at is not None else None
-        cnt = capi.c_int(0)
-        rc = getattr(self.L, "qpg_batch_%s_multi_device" % name)(self.h, C.byref(io), K, point, sel, C.byref(cnt))
-        return rc, int(cnt.value)
-
     def adjoints_device(self, gx, gy=None, active=None, want=ADJOINT_OUT, out=None, select=None, at=None, K=None):
         """adjoint_device for K pairs (gx, gy) in one call (qpg_batch_adjoint_multi_device, DESIGN.md section 18): gx [K][B][n], gy [K][B][m] or None;
         the outputs dq, dbmin, dbmax, dQx, dAx, flag, resid and passes have the same leading K, `active` (input and output, [B][m]), select and at are
         those of adjoint_device and shared by the directions.  K is the leading dimension of gx (pass K when gx is a raw address).  Slice k of every
         output holds the bits adjoint_device returns for slice k of the inputs; the set-up, the factor and the host's checks are paid once.  A
         direction that fails is flagged in its own slice; a member that is not solved is flagged in all of them.  `epoch` stays."""
-        nB, n, m = self.B, self.n, self.m
-        if gx is None:
-            raise ValueError("gx: expected a torch tensor or a raw address")
-        K = self._leading("adjoints_device", K, gx, gy)
-        shapes = dict(dq=((K, nB, n), "float64"), dbmin=((K, nB, m), "float64"), dbmax=((K, nB, m), "float64"), dQx=((K, nB, self.nnzQ), "float64"),
-                      dAx=((K, nB, self.nnzA), "float64"), active=((nB, m), "int64"), flag=((K, nB), "int64"), resid=((K, nB), "float64"),
-                      passes=((K, nB), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
-        if unknown:
-            raise ValueError("adjoints_device: unknown outputs %r" % sorted(unknown))
-        if out is None:
-            out = {k: self._empty(*shapes[k]) for k in want}
-        a = self._dev_args((gx, (K, nB, n), "gx", "float64"), (gy, (K, nB, m), "gy", "float64"), (active, (nB, m), "active", "int64"),
-                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.ADJOINT_OUT])
-        rc, cnt = self._multi_call("adjoint", capi.DeviceAdjoint(*a), K, select, at)
-        self._check(rc)
-        if select is not None:
-            out["n_selected"] = cnt
-        return out
+        return self._sens("adjoint", (gx, gy), active, want, out, select, at, True, K)
 
     def tangents_device(self, dq=None, dbmin=None, dbmax=None, dQx=None, dAx=None, active=None, want=TANGENT_OUT, out=None, select=None, at=None,
                         K=None):
@@ -537,26 +540,7 @@ class QpalmBatch:
         passes have the same leading K; `active` (input and output, [B][m]), select and at are those of tangent_device and shared by the directions.
         K is the leading dimension of the first tensor given (pass K with raw addresses).  Slice k of every output holds the bits tangent_device
         returns for slice k of the inputs.  `epoch` stays."""
-        nB, n, m = self.B, self.n, self.m
-        dirs = (dq, dbmin, dbmax, dQx, dAx)
-        if all(v is None for v in dirs):
-            raise ValueError("tangents_device: no direction (dq, dbmin, dbmax, dQx and dAx are all None)")
-        K = self._leading("tangents_device", K, *dirs)
-        shapes = dict(dx=((K, nB, n), "float64"), dy=((K, nB, m), "float64"), active=((nB, m), "int64"), flag=((K, nB), "int64"),
-                      resid=((K, nB), "float64"), passes=((K, nB), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
-        if unknown:
-            raise ValueError("tangents_device: unknown outputs %r" % sorted(unknown))
-        if out is None:
-            out = {k: self._empty(*shapes[k]) for k in want}
-        a = self._dev_args((dq, (K, nB, n), "dq", "float64"), (dbmin, (K, nB, m), "dbmin", "float64"), (dbmax, (K, nB, m), "dbmax", "float64"),
-                           (dQx, (K, nB, self.nnzQ), "dQx", "float64"), (dAx, (K, nB, self.nnzA), "dAx", "float64"), (active, (nB, m), "active", "int64"),
-                           *[(out.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.TANGENT_OUT])
-        rc, cnt = self._multi_call("tangent", capi.DeviceTangent(*a), K, select, at)
-        self._check(rc)
-        if select is not None:
-            out["n_selected"] = cnt
-        return out
+        return self._sens("tangent", (dq, dbmin, dbmax, dQx, dAx), active, want, out, select, at, True, K)
 
     def jacobian_device(self, wrt="q", mode="tangent", chunk=16, active=None, select=None, at=None):
         """The Jacobian of the stored solutions with respect to q, bmin or bmax, column block by column block through the multi calls: a dict with
@@ -585,17 +569,16 @@ class QpalmBatch:
             seed = self._empty((kc, nB, ndirs)).zero_()
             for k in range(kc):
                 seed[k, :, j0 + k] = 1.0
-            flag = self._empty((kc, nB), "int64").zero_()
             if mode == "tangent":
-                out = dict(dx=self._empty((kc, nB, n)).zero_(), dy=self._empty((kc, nB, m)).zero_(), flag=flag)
+                out = self._zeros("tangent", ("dx", "dy", "flag"), kc)
                 self.tangents_device(**{name: seed}, active=active, out=out, select=select, at=at)
                 res["dx"][:, :, j0:j0 + kc] = out["dx"].permute(1, 2, 0)
                 res["dy"][:, :, j0:j0 + kc] = out["dy"].permute(1, 2, 0)
             else:
-                out = {name: self._empty((kc, nB, p)).zero_(), "flag": flag}
+                out = self._zeros("adjoint", (name, "flag"), kc)
                 self.adjoints_device(seed, active=active, out=out, select=select, at=at)
                 res["dx"][:, j0:j0 + kc, :] = out[name].permute(1, 0, 2)
-            res["flag"] = torch.maximum(res["flag"], flag.max(dim=0).values)
+            res["flag"] = torch.maximum(res["flag"], out["flag"].max(dim=0).values)
         return res
 
     @property
@@ -611,8 +594,6 @@ class QpalmBatch:
     def sens_penalty(self, floor):
         self._check(self.L.qpg_batch_set_sens_penalty(self.h, float(floor)))
 
-    POLISH_OUT = ("x", "y", "res", "active", "flag", "resid", "passes")
-
     def polish_device(self, active_in=None, store=False, want=POLISH_OUT, out=None, select=None):
         """The exact solution at the final active set (qpg_batch_polish_device): per member one correction solve from its stored solution, a clip of
         wrong-signed multipliers and a verdict.  active_in: as `active` of adjoint_device.  want: which outputs to compute, among x [B][n], y [B][m]
@@ -622,21 +603,12 @@ class QpalmBatch:
         solution*, adjoint_device, tangent_device and warm_start_last read); info() still describes the solve.  Returns the dict.  `epoch` advances
         only when store changed a member (the flags then come to the host: one small transfer).  select: as for adjoint_device
         (qpg_batch_polish_subset_device): only selected members are polished and, with store, replaced; only their flags count for `epoch`."""
-        nB, n, m = self.B, self.n, self.m
-        shapes = dict(x=((nB, n), "float64"), y=((nB, m), "float64"), res=((nB, 4), "float64"), active=((nB, m), "int64"), flag=((nB,), "int64"),
-                      resid=((nB,), "float64"), passes=((nB,), "int64"))
-        unknown = set(out if out is not None else want) - set(shapes) - {"n_selected"}
-        if unknown:
-            raise ValueError("polish_device: unknown outputs %r" % sorted(unknown))
-        if out is None:
-            out = {k: self._empty(*shapes[k]) for k in want}
+        out, specs = self._outputs("polish", want, out, None, "polish_device: unknown outputs")
         flag = out.get("flag")
         if store and not hasattr(flag, "data_ptr"):   # the flags decide whether the stored solutions moved
-            flag = self._empty(*shapes["flag"])
-        given = dict(out, flag=flag)
-        a = self._dev_args((active_in, (nB, m), "active_in", "int64"), *[(given.get(k), shapes[k][0], "out " + k, shapes[k][1]) for k in self.POLISH_OUT])
-        io = capi.DevicePolish(a[0], 1 if store else 0, *a[1:])
-        rc, cnt = self._subset_call("polish", io, select)
+            flag = self._empty((self.B,), "int64")
+            specs = self._outputs("polish", (), dict(out, flag=flag), None, "polish_device: unknown outputs")[1]
+        rc, cnt = self._route("polish", self._io("polish", (active_in,), specs, value=1 if store else 0), select)
         self._check(rc)
         if store and bool(((flag == 0) if select is None else (flag == 0) & (select != 0)).any()):
             self.epoch += 1

@@ -53,17 +53,15 @@ class _QPFunction(torch.autograd.Function):
             rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm)
         else:
             # the step writes the selected rows only: x, y and the statuses of every member are read afterwards
-            rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm, out=dict(rejected=bt._empty((bt.B,), "int64").zero_()), select=select)
+            rc, out = bt.step_device(det(bmin), det(bmax), det(q), warm=layer.warm, out=bt._zeros("step", ("rejected",)), select=select)
             out["x"], out["y"] = bt.solution_device()
             out["status_val"], _ = bt.status_device()
         if rc != 0:
             raise ValueError("QPLayer: some member's bounds were refused (bmin > bmax): %r" % out["rejected"].nonzero().flatten().tolist())
         if layer.polish:
             # accepted members: the exact solution at their active set, returned and stored -- backward and jvp differentiate at the stored solution
-            pol_out = dict(x=out["x"], y=out["y"], res=bt._empty((bt.B, 4)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
-                           resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_())
-            if layer.replay:   # the set the polish used: the recorded point's active set
-                pol_out["active"] = bt._empty((bt.B, bt.m), "int64").zero_()
+            keys = ("res", "flag", "resid", "passes") + (("active",) if layer.replay else ())   # (the set the polish used: the recorded point's active set)
+            pol_out = dict(x=out["x"], y=out["y"], **bt._zeros("polish", keys))
             pol = bt.polish_device(store=True, select=select, out=pol_out)
             layer.last_polish = {k: pol[k] for k in ("flag", "res", "resid", "passes")}
         fctx.layer, fctx.epoch, fctx.select = layer, bt.epoch, select
@@ -80,44 +78,30 @@ class _QPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, gx, gy, _gs):
+        """the adjoint of the state the batch holds, or with replay=True at the recorded point of this forward pass: the batch may then have been stepped
+        any number of times since"""
         layer = fctx.layer
         bt = layer.batch
         if fctx.replay:
-            return _QPFunction._backward_replay(fctx, gx, gy)
-        if bt.epoch != fctx.epoch:
-            raise RuntimeError("QPLayer.backward: the batch was solved or updated again after this forward pass; its gradients are gone")
+            if bt.matrix_epoch != fctx.matrix_epoch:
+                raise RuntimeError("QPLayer.backward: the values of Q and A were updated after this forward pass; its recorded point is no longer valid")
+            x, y = fctx.saved_tensors
+            # the recorded statuses decide who is differentiated (the current ones are those of a later solve); the others keep zero rows
+            select = ((fctx.status_val == SOLVED) | (fctx.status_val == DUAL_TERMINATED)).to(torch.int64)
+            if fctx.select is not None:
+                select = select * (fctx.select != 0).to(torch.int64)
+            select, at = select.contiguous(), dict(at=(x.detach().contiguous(), y.detach().contiguous(), fctx.active))
+        else:
+            if bt.epoch != fctx.epoch:
+                raise RuntimeError("QPLayer.backward: the batch was solved or updated again after this forward pass; its gradients are gone")
+            select, at = getattr(fctx, "select", None), {}
         need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
         want = tuple(k for k, v in need.items() if v) + ("flag", "resid", "passes")
         gx = bt._empty((bt.B, bt.n)).zero_() if gx is None else gx.contiguous()
-        select = getattr(fctx, "select", None)
         if select is None:
             out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), want=want)
         else:   # rows of members that are not selected are not written: zero gradients
-            shapes = dict(dq=(bt.B, bt.n), dbmin=(bt.B, bt.m), dbmax=(bt.B, bt.m), dQx=(bt.B, bt.nnzQ), dAx=(bt.B, bt.nnzA), flag=(bt.B,), resid=(bt.B,), passes=(bt.B,))
-            zeros = {k: bt._empty(shapes[k], "int64" if k in ("flag", "passes") else "float64").zero_() for k in want}
-            out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=zeros, select=select)
-        layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
-        return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx")) + (None,)
-
-    @staticmethod
-    def _backward_replay(fctx, gx, gy):
-        """backward at the recorded point of this forward pass: the batch may have been stepped any number of times since"""
-        layer = fctx.layer
-        bt = layer.batch
-        if bt.matrix_epoch != fctx.matrix_epoch:
-            raise RuntimeError("QPLayer.backward: the values of Q and A were updated after this forward pass; its recorded point is no longer valid")
-        x, y = fctx.saved_tensors
-        need = dict(zip(("dq", "dbmin", "dbmax", "dQx", "dAx"), fctx.needs_input_grad[1:6]))
-        want = tuple(k for k, v in need.items() if v) + ("flag", "resid", "passes")
-        gx = bt._empty((bt.B, bt.n)).zero_() if gx is None else gx.contiguous()
-        # the recorded statuses decide who is differentiated (the current ones are those of a later solve); the others keep zero rows
-        select = ((fctx.status_val == SOLVED) | (fctx.status_val == DUAL_TERMINATED)).to(torch.int64)
-        if fctx.select is not None:
-            select = select * (fctx.select != 0).to(torch.int64)
-        shapes = dict(dq=(bt.B, bt.n), dbmin=(bt.B, bt.m), dbmax=(bt.B, bt.m), dQx=(bt.B, bt.nnzQ), dAx=(bt.B, bt.nnzA), flag=(bt.B,), resid=(bt.B,), passes=(bt.B,))
-        zeros = {k: bt._empty(shapes[k], "int64" if k in ("flag", "passes") else "float64").zero_() for k in want}
-        out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=zeros, select=select.contiguous(),
-                                at=(x.detach().contiguous(), y.detach().contiguous(), fctx.active))
+            out = bt.adjoint_device(gx, None if gy is None else gy.contiguous(), out=bt._zeros("adjoint", want), select=select, **at)
         layer.last_adjoint = {k: out[k] for k in ("flag", "resid", "passes")}
         return (None,) + tuple(out.get(k) for k in ("dq", "dbmin", "dbmax", "dQx", "dAx")) + (None,)
 
@@ -136,9 +120,7 @@ class _QPFunction(torch.autograd.Function):
         if select is None:
             out = bt.tangent_device(*d, want=("dx", "dy", "flag", "resid", "passes"))
         else:   # rows of members that are not selected are not written: zero tangents
-            zeros = dict(dx=bt._empty((bt.B, bt.n)).zero_(), dy=bt._empty((bt.B, bt.m)).zero_(), flag=bt._empty((bt.B,), "int64").zero_(),
-                         resid=bt._empty((bt.B,)).zero_(), passes=bt._empty((bt.B,), "int64").zero_())
-            out = bt.tangent_device(*d, out=zeros, select=select)
+            out = bt.tangent_device(*d, out=bt._zeros("tangent", ("dx", "dy", "flag", "resid", "passes")), select=select)
         layer.last_tangent = {k: out[k] for k in ("flag", "resid", "passes")}
         return out["dx"], out["dy"], None
 

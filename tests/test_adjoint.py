@@ -21,110 +21,10 @@ from qpalm_amd.capi import QpgError
 from qpalm_amd.solver import QpalmBatch
 from qpalm_amd.torch_layer import QPLayer
 from tests import adjoint_refs as R
+from tests.sens_helpers import (CASES, INVALID, REFUSED, REFUSED_WORD, ST, UNSUPPORTED, N, T, assert_complementary, assert_instance, padded, refused_mode,
+                                run_adjoint, small_batch, snapshot, solved)
+from tests.sens_helpers import judge_adjoint as judge
 from tests.sparse_gadgets import blocks_qp, gadget_qp
-
-ST = dict(eps_abs=1e-9, eps_rel=1e-9, verbose=0)
-U = 2.0 ** -53
-INVALID, UNSUPPORTED = -2, -5
-
-
-def dev(ctx):
-    return "cuda:0" if ctx.kind == "hip" else "cpu"
-
-
-def T(ctx, a, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev(ctx))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def padded(rows, width, dtype=np.float64):
-    out = np.zeros((len(rows), width), dtype=dtype)
-    for b, r in enumerate(rows):
-        out[b, :len(r)] = r
-    return out
-
-
-def assert_complementary(p, side, x, y):
-    """active rows: on their bound with |y| >= 1e-2; the others: slack >= 1e-2 and |y| <= 1e-8"""
-    ax = p.A_mat() @ x
-    act = side != 0
-    assert np.all(np.abs(y[act]) >= 1e-2)
-    assert np.all(np.abs(y[~act]) <= 1e-8)
-    slack = np.minimum(ax - p.bmin, p.bmax - ax)
-    assert np.all(slack[~act] >= 1e-2)
-    assert np.all(np.abs(np.where(side < 0, ax - p.bmin, ax - p.bmax))[act] <= 1e-6)
-
-
-def judge(ctx, what, p, side, x, y, gx, gy, out, b=0):
-    """member b of `out` (host arrays) against the reference at (x, y, side); prints the figures profiles/adjoint/accuracy.md records"""
-    n, m = p.n, p.m
-    zr, z64, J = R.reference(p, side, gx, gy)
-    scale = float(np.max(np.abs(zr))) or 1.0
-    err64 = float(np.max(np.abs(z64 - zr))) / scale
-    assert err64 <= 1e-10, "the generator's promise: float64 numpy itself solves K"
-    w = out["dbmin"][b, :m] + out["dbmax"][b, :m]
-    zk = np.concatenate([-out["dq"][b, :n], w[J]])
-    errk = float(np.max(np.abs(zk - zr))) / scale
-    tol = 8.0 * err64
-    print("ADJOINT-ACC | %s | %s | n=%d m=%d |J|=%d | err64 %.2e | kernel %.2e | passes %d | resid %.1e" %
-          (ctx.kind, what, n, m, len(J), err64, errk, int(out["passes"][b]), float(out["resid"][b])))
-    assert int(out["flag"][b]) == 0
-    assert errk <= tol, (what, errk, err64)
-    assert np.array_equal(out["active"][b, :m], side)
-    assert np.all(out["dbmin"][b, :m][side >= 0] == 0) and np.all(out["dbmax"][b, :m][side <= 0] == 0)
-    # the per-entry gradients are products of [u; w] with the solution: the same relative error, times the factors they are multiplied with
-    ref = R.gradients(p, side, x.astype(R.LD), y.astype(R.LD), zr)
-    ca, cq = np.repeat(np.arange(n), np.diff(p.Ap)), np.repeat(np.arange(n), np.diff(p.Qp))
-    fa = np.abs(y[p.Ai]) + np.abs(x[ca]) + 1.0
-    fq = np.abs(x[cq]) + np.abs(x[p.Qi]) + 1.0
-    for k, f in (("dAx", fa), ("dQx", fq)):
-        got, want = out[k][b], ref[k]
-        assert np.all(np.abs(got[:len(want)] - want) <= (tol * scale + 4 * U * scale) * f), (what, k)
-        assert np.all(got[len(want):] == 0), (what, k)
-    for k, width in (("dq", n), ("dbmin", m), ("dbmax", m), ("active", m)):
-        assert np.all(out[k][b, width:] == 0), (what, k)
-
-
-def run_adjoint(ctx, bt, gx, gy, sides, **kw):
-    out = bt.adjoint_device(T(ctx, gx), None if gy is None else T(ctx, gy), None if sides is None else T(ctx, sides, np.int64), **kw)
-    return {k: N(v) for k, v in out.items()}
-
-
-@dataclasses.dataclass(frozen=True)
-class Case:
-    n: int
-    m: int
-    nact: int
-    scaling: int
-    proximal: int
-    sides: str = "mixed"
-    equality: bool = False
-    gy: bool = True
-
-    @property
-    def id(self):
-        return "n%d-m%d-J%d%s-s%d-p%d" % (self.n, self.m, self.nact, "eq" if self.equality else "", self.scaling, self.proximal)
-
-
-CASES = [Case(1, 2, 1, 10, 0, sides="lower"), Case(1, 2, 0, 0, 1), Case(5, 8, 3, 10, 1), Case(31, 62, 12, 0, 1), Case(33, 16, 1, 10, 1, gy=False),
-         Case(64, 128, 63, 10, 0, equality=True), Case(65, 32, 20, 10, 0), Case(192, 96, 60, 0, 0), Case(193, 386, 90, 10, 1),
-         Case(256, 128, 0, 10, 1), Case(257, 514, 256, 0, 1, equality=True)]
-
-
-def assert_instance(ctx, bt, threads):
-    """the instance of the kernels the batch runs on: a silently different one fails here (the emulator has one, of 128 threads)"""
-    assert bt.launch_shape()[1] == (threads if ctx.kind == "hip" else 128), bt.launch_shape()
-
-
-def solved(ctx, probs, warm=None, **st):
-    bt = QpalmBatch(ctx, probs, ctx.default_settings(**dict(ST, **st)))
-    if warm is not None:
-        bt.warm_start(*warm)
-    bt.solve()
-    return bt
 
 
 # ---- 1. the arithmetic at a given active set, every size -----------------------------------------------------------------------------------------
@@ -276,17 +176,6 @@ def test_directional_derivative_against_central_differences(ctx):
 
 
 # ---- 6. the forward path does not see the adjoint -------------------------------------------------------------------------------------------------
-def snapshot(bt):
-    x, y = bt.solution()
-    infos, stats = bt.infos(), bt.stats_all()
-    out = dict(x=x.copy(), y=y.copy())
-    for k in ("status_val", "iter", "iter_out"):
-        out[k] = np.array([int(getattr(i, k)) for i in infos])
-    for k in ("n_refactor", "n_rank1", "n_factor_Q", "n_solve"):
-        out[k] = np.array([int(getattr(s, k)) for s in stats])
-    return out
-
-
 @pytest.mark.parametrize("mode,B,slots,warm", [("dense", 3, 512, "last"), ("dense", 5, 1, None), ("sparse", 2, 512, None), ("sparse", 3, 2, "last")])
 def test_next_step_is_bit_identical(ctx, mode, B, slots, warm):
     ctx.set_option("max_slots", slots)
@@ -320,31 +209,17 @@ def test_next_step_is_bit_identical(ctx, mode, B, slots, warm):
 
 
 # ---- 7. refusals and flags ------------------------------------------------------------------------------------------------------------------------
-def small_batch(ctx, B=1, **st):
-    probs = [R.planted_qp(12, 20, 5, 9950 + b)[0] for b in range(B)]
-    return QpalmBatch(ctx, probs, ctx.default_settings(**dict(ST, **st))), probs
-
-
-@pytest.mark.parametrize("which", ["kkt", "sparse_kkt", "coop", "nonconvex"])
+@pytest.mark.parametrize("which", REFUSED)
 def test_unsupported_modes_are_refused(ctx, which):
-    opts = dict(kkt=(), sparse_kkt=(("sparse_kkt", 1),), coop=(("coop", 1), ("small_workgroups", 0)), nonconvex=())[which]
-    st = dict(kkt=dict(factorization_method=0), sparse_kkt=dict(factorization_method=0), coop={}, nonconvex=dict(nonconvex=1))[which]
-    for k, v in opts:
-        ctx.set_option(k, v)
-    try:
-        bt, _ = small_batch(ctx, **st)
-        bt.solve()
+    with refused_mode(ctx, which) as bt:
         with pytest.raises(QpgError) as e:
             bt.adjoint_device(T(ctx, np.ones((1, 12))))
         assert e.value.code == UNSUPPORTED
-        assert dict(kkt="dense KKT", sparse_kkt="sparse_kkt", coop="coop", nonconvex="nonconvex")[which] in str(e.value)
-    finally:
-        ctx.set_option("sparse_kkt", 0)
-        ctx.set_option("small_workgroups", 1)
+        assert REFUSED_WORD[which] in str(e.value)
 
 
 def test_invalid_calls(ctx):
-    bt, probs = small_batch(ctx, B=2)
+    bt, _ = small_batch(ctx, B=2)
     gx = T(ctx, np.ones((2, 12)))
     bt.iterate(1)                                            # a solve in progress
     with pytest.raises(QpgError) as e:

@@ -28,9 +28,10 @@ from qpalm_amd.solver import QpalmBatch
 from qpalm_amd.torch_layer import QPLayer
 from tests import adjoint_refs as R
 from tests import polish_refs as PR
-from tests import test_adjoint as TA
+from tests.sens_helpers import (CASES, INVALID, REFUSED, REFUSED_WORD, UNSUPPORTED, N, T, assert_complementary, assert_instance, judge_adjoint, padded,
+                                refused_mode, run_adjoint, run_polish, small_batch, snapshot)
+from tests.sens_helpers import judge_polish as judge
 from tests.sparse_gadgets import blocks_qp, gadget_qp
-from tests.test_adjoint import CASES, INVALID, UNSUPPORTED, N, T, assert_instance, padded, snapshot
 
 LD = R.LD
 U = 2.0 ** -53
@@ -42,11 +43,6 @@ def loose(ctx, probs, **st):
     bt = QpalmBatch(ctx, probs, ctx.default_settings(**dict(LOOSE, **st)))
     bt.solve()
     return bt
-
-
-def run_polish(ctx, bt, sides=None, store=False, **kw):
-    out = bt.polish_device(None if sides is None else T(ctx, sides, np.int64), store=store, **kw)
-    return {k: N(v) for k, v in out.items()}
 
 
 def assert_inexact_but_right(p, side, x, y, zr=None, least=0.0):
@@ -64,33 +60,6 @@ def assert_inexact_but_right(p, side, x, y, zr=None, least=0.0):
         J = np.flatnonzero(side)
         err = float(np.max(np.abs(np.concatenate([x, y[J]]) - zr))) / (float(np.max(np.abs(zr))) or 1.0)
         assert err >= least, (err, least)
-
-
-def judge(ctx, what, p, side, x, y, out, b=0, improves=True):
-    """member b of `out` (host arrays) against the reference at the set `side`; (x, y): the stored solution before the call.  Prints the figures
-    profiles/polish/accuracy.md records."""
-    n, m = p.n, p.m
-    zr, z64, J = PR.candidate(p, side)
-    scale = float(np.max(np.abs(zr))) or 1.0
-    err64 = float(np.max(np.abs(z64 - zr))) / scale
-    assert err64 <= 1e-10, "the generator's promise: float64 numpy itself solves K"
-    tol = 8.0 * err64 + 4.0 * U
-    zk = np.concatenate([out["x"][b, :n], out["y"][b, :m][J]])
-    err0 = float(np.max(np.abs(np.concatenate([x, y[J]]) - zr))) / scale
-    errk = float(np.max(np.abs(zk - zr))) / scale
-    pri_old, dua_old, pri_new, dua_new = (float(v) for v in out["res"][b])
-    print("POLISH-ACC | %s | %s | n=%d m=%d |J|=%d | err64 %.2e | stored %.2e | polished %.2e | bound %.2e | passes %d | resid %.1e | pri %.2e -> %.2e | dua %.2e -> %.2e"
-          % (ctx.kind, what, n, m, len(J), err64, err0, errk, tol, int(out["passes"][b]), float(out["resid"][b]), pri_old, pri_new, dua_old, dua_new))
-    assert int(out["flag"][b]) == 0
-    assert errk <= tol, (what, errk, err64)
-    if improves:
-        assert (pri_new < pri_old) if pri_old > 0 else (pri_new == 0), (pri_old, pri_new)
-        assert (dua_new < dua_old) if dua_old > 0 else (dua_new == 0), (dua_old, dua_new)
-    assert np.array_equal(out["active"][b, :m], side)
-    assert np.all(out["y"][b, :m][side == 0] == 0)
-    for k, width in (("x", n), ("y", m), ("active", m)):
-        assert np.all(out[k][b, width:] == 0), (what, k)
-    return tol, err0
 
 
 # ---- 1. accuracy at every size where a kernel changes form; 2. the reported residuals (the same calls) ----------------------------------------------
@@ -306,10 +275,10 @@ def test_store_replaces_the_stored_solution_and_nothing_else(ctx):
     # the adjoint at the polished point: its own active-set rule finds J there, and the gradients are those of (x^, y^)
     rng = np.random.default_rng(31)
     gx, gy = rng.standard_normal((2, 20)), rng.standard_normal((2, 30))
-    adj = TA.run_adjoint(ctx, bt, gx, gy, None)
+    adj = run_adjoint(ctx, bt, gx, gy, None)
     for b, (p, side, _, _) in enumerate(planted):
-        TA.assert_complementary(p, side, out["x"][b], out["y"][b])
-        TA.judge(ctx, "after-polish[%d]" % b, p, side, out["x"][b], out["y"][b], gx[b], gy[b], adj, b)
+        assert_complementary(p, side, out["x"][b], out["y"][b])
+        judge_adjoint(ctx, "after-polish[%d]" % b, p, side, out["x"][b], out["y"][b], gx[b], gy[b], adj, b)
     # a third polish starts from the polished point: accepted again (a point at rounding level is not rejected for rounding) and as exact
     third = run_polish(ctx, bt, sides, store=True)
     assert third["flag"].tolist() == [0, 0]
@@ -321,26 +290,17 @@ def test_store_replaces_the_stored_solution_and_nothing_else(ctx):
 
 
 # ---- 7. invalid calls and refusals -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which", ["kkt", "sparse_kkt", "coop", "nonconvex"])
+@pytest.mark.parametrize("which", REFUSED)
 def test_unsupported_modes_are_refused(ctx, which):
-    opts = dict(kkt=(), sparse_kkt=(("sparse_kkt", 1),), coop=(("coop", 1), ("small_workgroups", 0)), nonconvex=())[which]
-    st = dict(kkt=dict(factorization_method=0), sparse_kkt=dict(factorization_method=0), coop={}, nonconvex=dict(nonconvex=1))[which]
-    for k, v in opts:
-        ctx.set_option(k, v)
-    try:
-        bt, _ = TA.small_batch(ctx, **st)
-        bt.solve()
+    with refused_mode(ctx, which) as bt:
         with pytest.raises(QpgError) as e:
             bt.polish_device()
         assert e.value.code == UNSUPPORTED and "qpg_batch_polish_device" in str(e.value)
-        assert dict(kkt="dense KKT", sparse_kkt="sparse_kkt", coop="coop", nonconvex="nonconvex")[which] in str(e.value)
-    finally:
-        ctx.set_option("sparse_kkt", 0)
-        ctx.set_option("small_workgroups", 1)
+        assert REFUSED_WORD[which] in str(e.value)
 
 
 def test_invalid_calls(ctx):
-    bt, _ = TA.small_batch(ctx, B=2)
+    bt, _ = small_batch(ctx, B=2)
     bt.iterate(1)                                            # a solve in progress
     with pytest.raises(QpgError) as e:
         bt.polish_device()
@@ -418,12 +378,12 @@ def test_layer_with_polish_differentiates_at_the_exact_solution(ctx):
         for polish in (True, False):
             g = grads[polish]
             if polish:
-                TA.judge(ctx, "layer-polish[%d]" % b, p, side, xe, ye, cx[b], cy[b], g, b)
+                judge_adjoint(ctx, "layer-polish[%d]" % b, p, side, xe, ye, cx[b], cy[b], g, b)
                 continue
             assert_inexact_but_right(p, side, g["x"][b], g["y"][b])
             with pytest.raises(AssertionError):
-                TA.judge(ctx, "layer-plain[%d]" % b, p, side, xe, ye, cx[b], cy[b], g, b)
-            # by how much: the rule's own bound on dAx (test_adjoint.judge), and the largest miss over the entries
+                judge_adjoint(ctx, "layer-plain[%d]" % b, p, side, xe, ye, cx[b], cy[b], g, b)
+            # by how much: the rule's own bound on dAx (sens_helpers.judge_adjoint), and the largest miss over the entries
             zr, z64, _ = R.reference(p, side, cx[b], cy[b])
             scale = float(np.max(np.abs(zr)))
             tol = 8.0 * float(np.max(np.abs(z64 - zr))) / scale

@@ -21,121 +21,13 @@ from qpalm_amd.solver import QpalmBatch
 from qpalm_amd.torch_layer import QPLayer
 from tests import adjoint_refs as R
 from tests import tangent_refs as TR
+from tests.sens_helpers import (INVALID, REFUSED, REFUSED_WORD, ST, UNSUPPORTED, N, T, adjoint_errors, assert_complementary, batch_direction, host, judge_adjoint,
+                                judge_tangent, other_data, padded, point, refused_mode, small_batch, snapshot)
 from tests.sparse_gadgets import blocks_qp
 
-ST = dict(eps_abs=1e-9, eps_rel=1e-9, verbose=0)
-U = 2.0 ** -53
 LD = R.LD
-INVALID, UNSUPPORTED = -2, -5
 ADJ_KEYS = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
 TAN_KEYS = ("dx", "dy", "active", "flag", "resid", "passes")
-
-
-def dev(ctx):
-    return "cuda:0" if ctx.kind == "hip" else "cpu"
-
-
-def T(ctx, a, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev(ctx))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def padded(rows, width, dtype=np.float64, fill=0):
-    out = np.full((len(rows), width), fill, dtype=dtype)
-    for b, r in enumerate(rows):
-        out[b, :len(r)] = r
-    return out
-
-
-def host(out):
-    return {k: (N(v) if hasattr(v, "detach") else v) for k, v in out.items()}
-
-
-def assert_complementary(p, side, x, y):
-    """active rows: on their bound with |y| >= 1e-2; the others: slack >= 1e-2 and |y| <= 1e-8"""
-    ax = p.A_mat() @ x
-    act = side != 0
-    assert np.all(np.abs(y[act]) >= 1e-2)
-    assert np.all(np.abs(y[~act]) <= 1e-8)
-    slack = np.minimum(ax - p.bmin, p.bmax - ax)
-    assert np.all(slack[~act] >= 1e-2)
-    assert np.all(np.abs(np.where(side < 0, ax - p.bmin, ax - p.bmax))[act] <= 1e-6)
-
-
-def adjoint_errors(p, side, gx, gy, out, b):
-    """(zr, scale, err64, errk): the reference [u; w_J] at `side`, float64 numpy's error on that system and that of member b of `out`"""
-    n, m = p.n, p.m
-    zr, z64, J = R.reference(p, side, gx, gy)
-    scale = float(np.max(np.abs(zr))) or 1.0
-    err64 = float(np.max(np.abs(z64 - zr))) / scale
-    w = out["dbmin"][b, :m] + out["dbmax"][b, :m]
-    zk = np.concatenate([-out["dq"][b, :n], w[J]])
-    return zr, scale, err64, float(np.max(np.abs(zk - zr))) / scale
-
-
-def judge_adjoint(ctx, what, p, side, x, y, gx, gy, out, b=0):
-    """member b of `out` (host arrays) against the reference at the point (x, y, side): the rule of tests/test_adjoint.py"""
-    n, m = p.n, p.m
-    zr, scale, err64, errk = adjoint_errors(p, side, gx, gy, out, b)
-    assert err64 <= 1e-10, "the generator's promise: float64 numpy itself solves K"
-    tol = 8.0 * err64
-    print("SENS-AT | %s | adjoint %s | n=%d m=%d |J|=%d | err64 %.2e | kernel %.2e | passes %d | resid %.1e" %
-          (ctx.kind, what, n, m, int(np.count_nonzero(side)), err64, errk, int(out["passes"][b]), float(out["resid"][b])))
-    assert int(out["flag"][b]) == 0
-    assert errk <= tol, (what, errk, err64)
-    assert np.array_equal(out["active"][b, :m], side)
-    assert np.all(out["dbmin"][b, :m][side >= 0] == 0) and np.all(out["dbmax"][b, :m][side <= 0] == 0)
-    # the per-entry gradients are products of [u; w] with the point: the same relative error, times the factors they are multiplied with
-    ref = R.gradients(p, side, x.astype(LD), y.astype(LD), zr)
-    ca, cq = np.repeat(np.arange(n), np.diff(p.Ap)), np.repeat(np.arange(n), np.diff(p.Qp))
-    fa = np.abs(y[p.Ai]) + np.abs(x[ca]) + 1.0
-    fq = np.abs(x[cq]) + np.abs(x[p.Qi]) + 1.0
-    for k, f in (("dAx", fa), ("dQx", fq)):
-        got, want = out[k][b], ref[k]
-        assert np.all(np.abs(got[:len(want)] - want) <= (tol * scale + 4 * U * scale) * f), (what, k)
-        assert np.all(got[len(want):] == 0), (what, k)
-    for k, width in (("dq", n), ("dbmin", m), ("dbmax", m), ("active", m)):
-        assert np.all(out[k][b, width:] == 0), (what, k)
-
-
-def judge_tangent(ctx, what, p, side, x, y, d, out, b=0):
-    """the rule of tests/test_tangent.py"""
-    n, m = p.n, p.m
-    zr, z64, J = TR.tangent(p, side, x, y, d)
-    scale = float(np.max(np.abs(zr))) or 1.0
-    err64 = float(np.max(np.abs(z64 - zr))) / scale
-    assert err64 <= 1e-10, "the generator's promise: float64 numpy itself solves K"
-    zk = np.concatenate([out["dx"][b, :n], out["dy"][b, :m][J]])
-    errk = float(np.max(np.abs(zk - zr))) / scale
-    print("SENS-AT | %s | tangent %s | n=%d m=%d |J|=%d | err64 %.2e | kernel %.2e | passes %d | resid %.1e" %
-          (ctx.kind, what, n, m, len(J), err64, errk, int(out["passes"][b]), float(out["resid"][b])))
-    assert int(out["flag"][b]) == 0
-    assert errk <= 8.0 * err64, (what, errk, err64)
-    assert np.array_equal(out["active"][b, :m], side)
-    assert np.all(out["dy"][b, :m][side == 0] == 0)
-    for k, width in (("dx", n), ("dy", m), ("active", m)):
-        assert np.all(out[k][b, width:] == 0), (what, k)
-
-
-def batch_direction(bt, dirs):
-    """per-member directions (tangent_refs.direction) as the [B][stride] arrays of the call; what lies beyond a member's own sizes is NaN: never read"""
-    width = dict(dq=bt.n, dbmin=bt.m, dbmax=bt.m, dQx=bt.nnzQ, dAx=bt.nnzA)
-    out = {}
-    for k in TR.KEYS:
-        a = np.full((len(dirs), width[k]), np.nan)
-        for b, d in enumerate(dirs):
-            a[b, :len(d[k])] = d[k]
-        out[k] = a
-    return out
-
-
-def point(bt):
-    """the point of the batch's latest solve: (x, y, active) in device memory"""
-    x, y = bt.solution_device()
-    return x, y, bt.active_device()
 
 
 # ---- the shapes of checks 1 and 2 --------------------------------------------------------------------------------------------------------------------
@@ -248,19 +140,6 @@ def test_same_state_same_bits(ctx, shape):
 
 
 # ---- 3. an earlier solve ------------------------------------------------------------------------------------------------------------------------------
-def other_data(planted, which, seed):
-    """q and bounds planted on the same Q and A with another active set: J1 without its first (which = 0) or its last (which = 1) row"""
-    out = []
-    for b, (p, side, _, _) in enumerate(planted):
-        J = np.flatnonzero(side)
-        s2 = side.copy()
-        s2[J[0] if which == 0 else J[-1]] = 0
-        p2, x2, y2 = R.plant(p.Q_full(), p.A_mat(), s2, seed + b)
-        assert np.array_equal(p2.Ax, p.Ax) and np.array_equal(p2.Qx, p.Qx)     # the same matrices: only q and the bounds move
-        out.append((p2, s2, x2, y2))
-    return out
-
-
 @pytest.mark.parametrize("floor", [0.0, 1e6])
 def test_an_earlier_solve(ctx, floor):
     planted = [R.planted_qp(n, m, k, 9500 + 11 * b) for b, (n, m, k) in enumerate([(33, 50, 20), (20, 30, 7), (5, 8, 3)])]
@@ -294,8 +173,8 @@ def test_an_earlier_solve(ctx, floor):
     now = host(bt.adjoint_device(T(ctx, gx), T(ctx, gy)))         # the plain call at this moment: the gradients of the THIRD solve
     for b, (p, side, _, _) in enumerate(planted):
         xb, yb = x1[b, :p.n], y1[b, :p.m]
-        judge_adjoint(ctx, "P1[%d] floor %g" % (b, floor), p, side, xb, yb, gx[b, :p.n], gy[b, :p.m], out, b)
-        judge_tangent(ctx, "P1[%d] floor %g" % (b, floor), p, side, xb, yb, dirs[b], tan, b)
+        judge_adjoint(ctx, "adjoint P1[%d] floor %g" % (b, floor), p, side, xb, yb, gx[b, :p.n], gy[b, :p.m], out, b, tag="SENS-AT")
+        judge_tangent(ctx, "tangent P1[%d] floor %g" % (b, floor), p, side, xb, yb, dirs[b], tan, b, tag="SENS-AT")
         _, _, err64, errk = adjoint_errors(p, side, gx[b, :p.n], gy[b, :p.m], now, b)
         print("SENS-AT | %s | the plain adjoint two solves later against P1[%d] | err64 %.2e | kernel %.2e" % (ctx.kind, b, err64, errk))
         assert int(now["flag"][b]) == 0 and errk > 8.0 * err64     # ... which are not P1's: the check discriminates
@@ -303,17 +182,6 @@ def test_an_earlier_solve(ctx, floor):
 
 
 # ---- 4. state: the call neither reads nor moves what the next solve starts from ----------------------------------------------------------------------
-def snapshot(bt):
-    x, y = bt.solution()
-    infos, stats = bt.infos(), bt.stats_all()
-    out = dict(x=x.copy(), y=y.copy())
-    for k in ("status_val", "iter", "iter_out"):
-        out[k] = np.array([int(getattr(i, k)) for i in infos])
-    for k in ("n_refactor", "n_rank1", "n_factor_Q", "n_solve"):
-        out[k] = np.array([int(getattr(s, k)) for s in stats])
-    return out
-
-
 @pytest.mark.parametrize("mode,B,slots,warm", [("dense", 3, 512, "last"), ("dense", 5, 1, None), ("sparse", 2, 512, None), ("sparse", 3, 2, "last")])
 def test_next_step_is_bit_identical(ctx, mode, B, slots, warm):
     ctx.set_option("max_slots", slots)
@@ -353,11 +221,6 @@ def test_next_step_is_bit_identical(ctx, mode, B, slots, warm):
 
 
 # ---- 5. refusals and flags ------------------------------------------------------------------------------------------------------------------------------
-def small_batch(ctx, B=1, **st):
-    planted = [R.planted_qp(12, 20, 5, 9950 + b) for b in range(B)]
-    return QpalmBatch(ctx, [q[0] for q in planted], ctx.default_settings(**dict(ST, **st))), planted
-
-
 def at_calls(ctx, bt, at):
     """the three new calls, each as a thunk"""
     gx = T(ctx, np.ones((bt.B, bt.n)))
@@ -369,23 +232,14 @@ def fake_point(ctx, bt):
     return T(ctx, np.zeros((bt.B, bt.n))), T(ctx, np.zeros((bt.B, bt.m))), T(ctx, np.zeros((bt.B, bt.m)), np.int64)
 
 
-@pytest.mark.parametrize("which", ["kkt", "sparse_kkt", "coop", "nonconvex"])
+@pytest.mark.parametrize("which", REFUSED)
 def test_unsupported_modes_are_refused(ctx, which):
-    opts = dict(kkt=(), sparse_kkt=(("sparse_kkt", 1),), coop=(("coop", 1), ("small_workgroups", 0)), nonconvex=())[which]
-    st = dict(kkt=dict(factorization_method=0), sparse_kkt=dict(factorization_method=0), coop={}, nonconvex=dict(nonconvex=1))[which]
-    for k, v in opts:
-        ctx.set_option(k, v)
-    try:
-        bt, _ = small_batch(ctx, **st)
-        bt.solve()
+    with refused_mode(ctx, which) as bt:
         for name, call in at_calls(ctx, bt, fake_point(ctx, bt)):
             with pytest.raises(QpgError) as e:
                 call()
             assert e.value.code == UNSUPPORTED, name
-            assert dict(kkt="dense KKT", sparse_kkt="sparse_kkt", coop="coop", nonconvex="nonconvex")[which] in str(e.value)
-    finally:
-        ctx.set_option("sparse_kkt", 0)
-        ctx.set_option("small_workgroups", 1)
+            assert REFUSED_WORD[which] in str(e.value)
 
 
 def test_invalid_calls(ctx):
@@ -504,8 +358,8 @@ def test_a_point_that_is_not_finite(ctx):
         assert np.array_equal(got["active"][1], N(act)[1]) and np.array_equal(got_t["active"][1], N(act)[1])   # the set given
         for b in (0, 2):
             p, side, _, _ = planted[b]
-            judge_adjoint(ctx, "NaN-neighbour[%d]" % b, p, side, N(x)[b, :p.n], N(y)[b, :p.m], gx[b, :p.n], gy[b, :p.m], got, b)
-            judge_tangent(ctx, "NaN-neighbour[%d]" % b, p, side, N(x)[b, :p.n], N(y)[b, :p.m], dirs[b], got_t, b)
+            judge_adjoint(ctx, "adjoint NaN-neighbour[%d]" % b, p, side, N(x)[b, :p.n], N(y)[b, :p.m], gx[b, :p.n], gy[b, :p.m], got, b, tag="SENS-AT")
+            judge_tangent(ctx, "tangent NaN-neighbour[%d]" % b, p, side, N(x)[b, :p.n], N(y)[b, :p.m], dirs[b], got_t, b, tag="SENS-AT")
             for k in ADJ_KEYS:
                 assert np.array_equal(got[k][b], clean[k][b]), k
 

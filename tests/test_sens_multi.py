@@ -29,9 +29,9 @@ from qpalm_amd import capi
 from qpalm_amd.capi import QpgError
 from qpalm_amd.solver import QpalmBatch
 from tests import adjoint_refs as R
+from tests.sens_helpers import (INVALID, REFUSED, REFUSED_WORD, ST, UNSUPPORTED, N, T, assert_complementary, assert_instance, host, other_data, padded, point,
+                                refused_mode, small_batch, snapshot, solved)
 from tests.sparse_gadgets import blocks_qp
-from tests.test_adjoint import INVALID, ST, UNSUPPORTED, N, T, assert_complementary, assert_instance, padded, small_batch, snapshot, solved
-from tests.test_sens_at import other_data, point
 
 ADJ_KEYS = ("dq", "dbmin", "dbmax", "dQx", "dAx", "active", "flag", "resid", "passes")
 TAN_KEYS = ("dx", "dy", "active", "flag", "resid", "passes")
@@ -39,10 +39,6 @@ TAN_IN = ("dq", "dbmin", "dbmax", "dQx", "dAx")
 SHARED = ("active",)          # written once per call: not per direction
 FLOORS = (0.0, 1e6)
 U = 2.0 ** -53
-
-
-def host(out):
-    return {k: (N(v) if hasattr(v, "detach") else v) for k, v in out.items()}
 
 
 def same_bits(a, b):
@@ -415,15 +411,9 @@ def test_jacobian_of_a_mixed_batch(ctx):
 
 
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which", ["kkt", "sparse_kkt", "coop", "nonconvex"])
+@pytest.mark.parametrize("which", REFUSED)
 def test_unsupported_modes_are_refused(ctx, which):
-    opts = dict(kkt=(), sparse_kkt=(("sparse_kkt", 1),), coop=(("coop", 1), ("small_workgroups", 0)), nonconvex=())[which]
-    st = dict(kkt=dict(factorization_method=0), sparse_kkt=dict(factorization_method=0), coop={}, nonconvex=dict(nonconvex=1))[which]
-    for k, v in opts:
-        ctx.set_option(k, v)
-    try:
-        bt, _ = small_batch(ctx, **st)
-        bt.solve()
+    with refused_mode(ctx, which) as bt:
         g = T(ctx, np.ones((2, 1, 12)))
         for call, single in ((lambda: bt.adjoints_device(g), lambda: bt.adjoint_device(g[0])), (lambda: bt.tangents_device(dq=g), lambda: bt.tangent_device(dq=g[0]))):
             with pytest.raises(QpgError) as e:
@@ -431,14 +421,11 @@ def test_unsupported_modes_are_refused(ctx, which):
             with pytest.raises(QpgError) as e1:
                 single()
             assert e.value.code == e1.value.code == UNSUPPORTED
-            assert dict(kkt="dense KKT", sparse_kkt="sparse_kkt", coop="coop", nonconvex="nonconvex")[which] in str(e.value)
-    finally:
-        ctx.set_option("sparse_kkt", 0)
-        ctx.set_option("small_workgroups", 1)
+            assert REFUSED_WORD[which] in str(e.value)
 
 
 def test_invalid_calls(ctx):
-    bt, probs = small_batch(ctx, B=2)
+    bt, _ = small_batch(ctx, B=2)
     L, h = bt.L, bt.h
     g = T(ctx, np.ones((3, 2, 12)))
     bt.iterate(1)                                            # a solve in progress

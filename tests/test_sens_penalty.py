@@ -27,11 +27,9 @@ from qpalm_amd.solver import QpalmBatch
 from qpalm_amd.torch_layer import QPLayer
 from tests import adjoint_refs as R
 from tests import tangent_refs as TR
-from tests import test_adjoint as TA
-from tests import test_polish as TP
-from tests import test_tangent as TT
+from tests.sens_helpers import (CASES, INVALID, ST, UNSUPPORTED, Case, N, T, assert_complementary, assert_instance, batch_direction, judge_adjoint, judge_polish,
+                                padded, run_adjoint, run_polish, run_tangent, small_batch, snapshot, solved, tangent_measure)
 from tests.sparse_gadgets import blocks_qp
-from tests.test_adjoint import CASES, INVALID, ST, UNSUPPORTED, Case, N, T, assert_complementary, assert_instance, padded, snapshot, solved
 
 LD = R.LD
 REC = 1e6
@@ -155,7 +153,7 @@ def test_a_loose_solve_no_longer_runs_into_the_pass_cap(ctx):
             assert np.array_equal(fast["active"], slow["active"]) and np.array_equal(fast["active"], sides)
             if mode == "polish":
                 for b, (p, side, _, _) in enumerate(planted):
-                    TP.judge(ctx, "loose[%d]" % b, p, side, *stored[b], fast, b, improves=False)
+                    judge_polish(ctx, "loose[%d]" % b, p, side, *stored[b], fast, b, improves=False)
         # ... and by the engine's own rule on the stored solution (sigma_inv of the solve): the same set with either floor
         by_rule = call(ctx, bt, "polish", None, gx, gy)["active"]
         set_floor(bt, REC)
@@ -175,8 +173,8 @@ def test_accuracy_with_the_recommended_floor(ctx, case):
     assert_complementary(p, side, x, y)
     rng = np.random.default_rng(case.n)
     gx, gy = rng.standard_normal((1, case.n)), (rng.standard_normal((1, case.m)) if case.gy else None)
-    adj = TA.run_adjoint(ctx, bt, gx, gy, side[None, :])
-    TA.judge(ctx, "floor-" + case.id, p, side, x, y, gx[0], None if gy is None else gy[0], adj)
+    adj = run_adjoint(ctx, bt, gx, gy, side[None, :])
+    judge_adjoint(ctx, "floor-" + case.id, p, side, x, y, gx[0], None if gy is None else gy[0], adj)
     duality(ctx, bt, [(p, side)], gx, gy if gy is not None else np.zeros((1, case.m)), side[None, :], adj if gy is not None else None, "floor-" + case.id)
 
 
@@ -184,15 +182,15 @@ def duality(ctx, bt, members, gx, gy, sides, adj, what):
     """<gx, dx> + <gy, dy> = <adjoint outputs of (gx, gy), direction>, to the tolerance of tests/test_tangent.py's duality check"""
     rng = np.random.default_rng(22)
     dirs = [TR.direction(p, rng) for p, _ in members]
-    tan = TT.run_tangent(ctx, bt, TT.batch_direction(bt, dirs), sides)
+    tan = run_tangent(ctx, bt, batch_direction(bt, dirs), sides)
     if adj is None:
-        adj = TA.run_adjoint(ctx, bt, gx, gy, sides)
+        adj = run_adjoint(ctx, bt, gx, gy, sides)
     assert np.all(tan["flag"] == 0) and np.all(adj["flag"] == 0)
     assert np.all(tan["passes"] <= PASS_BOUND) and np.all(adj["passes"] <= PASS_BOUND), (tan["passes"], adj["passes"])
     for b, (p, side) in enumerate(members):
         n, m = p.n, p.m
         x, y = bt.solution_of(b)
-        _, J, scale_t, err_t = TT.measure(p, side, x, y, dirs[b])
+        _, J, scale_t, err_t = tangent_measure(p, side, x, y, dirs[b])
         za, z64a, _ = R.reference(p, side, gx[b, :n], gy[b, :m])
         scale_a = float(np.max(np.abs(za))) or 1.0
         err_a = float(np.max(np.abs(z64a - za))) / scale_a
@@ -212,14 +210,14 @@ def test_accuracy_no_active_row_no_constraint_and_a_padded_member(ctx):
     rng = np.random.default_rng(5)
     gx, gy = rng.standard_normal((bt.B, bt.n)), rng.standard_normal((bt.B, bt.m))
     sides = padded([q[1] for q in planted], bt.m, np.int64)
-    adj = TA.run_adjoint(ctx, bt, gx, gy, sides)
-    pol = TP.run_polish(ctx, bt, sides)
+    adj = run_adjoint(ctx, bt, gx, gy, sides)
+    pol = run_polish(ctx, bt, sides)
     assert np.all(pol["passes"] <= PASS_BOUND), pol["passes"]
     for b, (p, side, _, _) in enumerate(planted):
         x, y = bt.solution_of(b)
         assert_complementary(p, side, x, y)
-        TA.judge(ctx, "floor-mixed[%d]" % b, p, side, x, y, gx[b, :p.n], gy[b, :p.m], adj, b)
-        TP.judge(ctx, "floor-mixed[%d]" % b, p, side, x, y, pol, b, improves=False)
+        judge_adjoint(ctx, "floor-mixed[%d]" % b, p, side, x, y, gx[b, :p.n], gy[b, :p.m], adj, b)
+        judge_polish(ctx, "floor-mixed[%d]" % b, p, side, x, y, pol, b, improves=False)
     duality(ctx, bt, [(q[0], q[1]) for q in planted], gx, gy, sides, adj, "floor-mixed")
     # m = 0: nothing for the floor to act on
     p0 = R.planted_qp(12, 20, 0, 9990)[0]
@@ -246,8 +244,8 @@ def test_accuracy_on_the_sparse_factor(ctx):
         assert_complementary(p, side, x, y)
         rng = np.random.default_rng(3)
         gx, gy = rng.standard_normal((1, p.n)), rng.standard_normal((1, p.m))
-        adj = TA.run_adjoint(ctx, bt, gx, gy, side[None, :])
-        TA.judge(ctx, "floor-sparse", p, side, x, y, gx[0], gy[0], adj)
+        adj = run_adjoint(ctx, bt, gx, gy, side[None, :])
+        judge_adjoint(ctx, "floor-sparse", p, side, x, y, gx[0], gy[0], adj)
         duality(ctx, bt, [(p, side)], gx, gy, side[None, :], adj, "floor-sparse")
     finally:
         ctx.set_option("sparse_factor", -1)
@@ -369,7 +367,7 @@ def test_dependent_active_rows(ctx):
     sides = np.zeros((1, 20), np.int64)
     sides[0, i0], sides[0, i1] = -1, -1
     gx = np.ones((1, 12))
-    out = TA.run_adjoint(ctx, bt, gx, None, sides)                      # consistent: the unique u, and the sum of the two rows' w
+    out = run_adjoint(ctx, bt, gx, None, sides)                      # consistent: the unique u, and the sum of the two rows' w
     assert int(out["flag"][0]) == 0
     assert all(np.all(np.isfinite(v)) for v in out.values())
     one = np.zeros(20, int)
@@ -383,7 +381,7 @@ def test_dependent_active_rows(ctx):
     assert errk <= 8 * err64
     gy = np.zeros((1, 20))                                              # inconsistent: no solution, with any preconditioner
     gy[0, i0], gy[0, i1] = 1.0, -1.0
-    out = TA.run_adjoint(ctx, bt, gx, gy, sides)
+    out = run_adjoint(ctx, bt, gx, gy, sides)
     assert int(out["flag"][0]) == 1
     for k in ("dq", "dbmin", "dbmax", "dQx", "dAx"):
         assert np.all(out[k] == 0), k
@@ -439,14 +437,15 @@ def test_layer_with_polish_and_a_floor(ctx):
         for b, (p, side, _, _) in enumerate(planted):
             xb, yb = bt.solution_of(b)
             assert np.array_equal(N(x)[b, :p.n], xb[:p.n])
-            TA.judge(ctx, "floor-layer[%d]" % b, p, side, xb[:p.n], yb[:p.m], N(cx)[b, :p.n], N(cy)[b, :p.m], own, b)
+            judge_adjoint(ctx, "floor-layer[%d]" % b, p, side, xb[:p.n], yb[:p.m], N(cx)[b, :p.n], N(cy)[b, :p.m], own, b)
     finally:
         ctx.set_option("max_slots", 512)
 
 
 # ---- 7. the interface ------------------------------------------------------------------------------------------------------------------------------
 def test_interface(ctx):
-    bt, probs = TA.small_batch(ctx, B=2)
+    bt, planted = small_batch(ctx, B=2)
+    probs = [q[0] for q in planted]
     L = bt.L
     assert bt.sens_penalty == 0.0
     bt.sens_penalty = 1e6
@@ -486,7 +485,7 @@ def test_interface(ctx):
 
 
 def test_refused_batches_store_the_floor_and_still_refuse(ctx):
-    bt, _ = TA.small_batch(ctx, factorization_method=0)
+    bt, _ = small_batch(ctx, factorization_method=0)
     bt.solve()
     set_floor(bt, 1e6)
     with pytest.raises(QpgError) as e:

@@ -18,8 +18,8 @@ from qpalm_amd.capi import QpgError
 from qpalm_amd.solver import QpalmBatch
 from qpalm_amd.torch_layer import QPLayer
 from tests import adjoint_refs as R
+from tests.sens_helpers import INVALID, UNSUPPORTED, N, T, assert_instance, padded, snapshot
 from tests.sparse_gadgets import blocks_qp
-from tests.test_adjoint import INVALID, UNSUPPORTED, N, T, assert_instance, padded, snapshot
 
 ST = dict(eps_abs=1e-6, eps_rel=1e-6, verbose=0)
 VECS = ("x", "y", "q", "bmin", "bmax", "sigma")
@@ -87,7 +87,7 @@ class Twin:
 
 
 def state(bt):
-    """snapshot() of tests/test_adjoint.py plus the vectors of every member a caller can read"""
+    """snapshot() of tests/sens_helpers.py plus the vectors of every member a caller can read"""
     out = snapshot(bt)
     for k in VECS:
         out["vec_" + k] = np.array([bt.vec(k, b) for b in range(bt.B)])

@@ -25,55 +25,13 @@ from qpalm_amd.torch_layer import QPLayer, _QPFunction
 from tests import adjoint_refs as R
 from tests import tangent_refs as TR
 from tests.sparse_gadgets import blocks_qp, gadget_qp
-from tests.test_adjoint import INVALID, ST, UNSUPPORTED, N, T, assert_complementary, assert_instance, padded, small_batch, snapshot, solved
+from tests.sens_helpers import (INVALID, REFUSED, REFUSED_WORD, ST, UNSUPPORTED, N, T, assert_complementary, assert_instance, batch_direction, padded,
+                                refused_mode, run_tangent, small_batch, snapshot, solved)
+from tests.sens_helpers import judge_tangent as judge
+from tests.sens_helpers import tangent_measure as measure
 
 LD = R.LD
 OUT = ("dx", "dy", "active", "flag", "resid", "passes")
-
-
-def run_tangent(ctx, bt, d, sides, **kw):
-    """d: dict of host arrays [B][...] (absent / None = not passed)"""
-    args = {k: (None if d.get(k) is None else T(ctx, d[k])) for k in TR.KEYS}
-    out = bt.tangent_device(active=None if sides is None else T(ctx, sides, np.int64), **args, **kw)
-    return {k: N(v) for k, v in out.items()}
-
-
-def batch_direction(bt, dirs):
-    """per-member directions (tangent_refs.direction) as the [B][stride] arrays of the call; what lies beyond a member's own sizes is NaN: never read"""
-    width = dict(dq=bt.n, dbmin=bt.m, dbmax=bt.m, dQx=bt.nnzQ, dAx=bt.nnzA)
-    out = {}
-    for k in TR.KEYS:
-        if all(d.get(k) is None for d in dirs):
-            continue
-        a = np.full((len(dirs), width[k]), np.nan)
-        for b, d in enumerate(dirs):
-            a[b, :len(d[k])] = d[k]
-        out[k] = a
-    return out
-
-
-def measure(p, side, x, y, d):
-    zr, z64, J = TR.tangent(p, side, x, y, d)
-    scale = float(np.max(np.abs(zr))) or 1.0
-    err64 = float(np.max(np.abs(z64 - zr))) / scale
-    return zr, J, scale, err64
-
-
-def judge(ctx, what, p, side, x, y, d, out, b=0):
-    """member b of `out` (host arrays) against the reference at (x, y, side); prints the figures profiles/tangent/accuracy.md records"""
-    n, m = p.n, p.m
-    zr, J, scale, err64 = measure(p, side, x, y, d)
-    assert err64 <= 1e-10, "the generator's promise: float64 numpy itself solves K"
-    zk = np.concatenate([out["dx"][b, :n], out["dy"][b, :m][J]])
-    errk = float(np.max(np.abs(zk - zr))) / scale
-    print("TANGENT-ACC | %s | %s | n=%d m=%d |J|=%d | err64 %.2e | kernel %.2e | passes %d | resid %.1e" %
-          (ctx.kind, what, n, m, len(J), err64, errk, int(out["passes"][b]), float(out["resid"][b])))
-    assert int(out["flag"][b]) == 0
-    assert errk <= 8.0 * err64, (what, errk, err64)
-    assert np.array_equal(out["active"][b, :m], side)
-    assert np.all(out["dy"][b, :m][side == 0] == 0)
-    for k, width in (("dx", n), ("dy", m), ("active", m)):
-        assert np.all(out[k][b, width:] == 0), (what, k)
 
 
 # ---- 0. the reference itself, without a backend: duality with the adjoint's reference ------------------------------------------------------------
@@ -360,26 +318,17 @@ def test_next_step_is_bit_identical(ctx, mode, B, slots, then_adjoint):
 
 
 # ---- 11. flags and refusals ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which", ["kkt", "sparse_kkt", "coop", "nonconvex"])
+@pytest.mark.parametrize("which", REFUSED)
 def test_unsupported_modes_are_refused(ctx, which):
-    opts = dict(kkt=(), sparse_kkt=(("sparse_kkt", 1),), coop=(("coop", 1), ("small_workgroups", 0)), nonconvex=())[which]
-    st = dict(kkt=dict(factorization_method=0), sparse_kkt=dict(factorization_method=0), coop={}, nonconvex=dict(nonconvex=1))[which]
-    for k, v in opts:
-        ctx.set_option(k, v)
-    try:
-        bt, _ = small_batch(ctx, **st)
-        bt.solve()
+    with refused_mode(ctx, which) as bt:
         with pytest.raises(QpgError) as e:
             bt.tangent_device(dq=T(ctx, np.ones((1, 12))))
         assert e.value.code == UNSUPPORTED and "qpg_batch_tangent_device" in str(e.value)
-        assert dict(kkt="dense KKT", sparse_kkt="sparse_kkt", coop="coop", nonconvex="nonconvex")[which] in str(e.value)
-    finally:
-        ctx.set_option("sparse_kkt", 0)
-        ctx.set_option("small_workgroups", 1)
+        assert REFUSED_WORD[which] in str(e.value)
 
 
 def test_invalid_calls(ctx):
-    bt, probs = small_batch(ctx, B=2)
+    bt, _ = small_batch(ctx, B=2)
     dq = T(ctx, np.ones((2, 12)))
     bt.iterate(1)                                            # a solve in progress
     with pytest.raises(QpgError) as e:

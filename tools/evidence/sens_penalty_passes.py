@@ -76,7 +76,7 @@ def child(a):
         report(a.child, bt, None)
     else:
         from tests import adjoint_refs as R
-        from tests.test_adjoint import CASES, ST
+        from tests.sens_helpers import CASES, ST
         for c in CASES:
             if c.n > a.nmax:
                 continue

@@ -29,7 +29,7 @@ def main():
     from qpalm_amd.solver import Context, QpalmBatch
     from tests import adjoint_refs as R
     from tests.sparse_gadgets import blocks_qp, gadget_qp
-    from tests.test_adjoint import CASES, ST, padded
+    from tests.sens_helpers import CASES, ST, padded
     ctx = Context(0, lib_path=a.lib)
     dev = "cpu" if ctx.backend == "host-emulation" else "cuda:0"
     put = lambda v, dt=np.float64: torch.from_numpy(np.ascontiguousarray(v, dtype=dt)).to(dev)
