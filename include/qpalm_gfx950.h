@@ -490,6 +490,11 @@ int qpg_ldlsolveLD_neg_dphi(qpg_batch *bt, qpg_int idx);
 int qpg_compute_residuals(qpg_batch *bt, qpg_int idx);
 int qpg_set_active_constraints(qpg_batch *bt, qpg_int idx);
 int qpg_exact_linesearch(qpg_batch *bt, qpg_int idx, qpg_float *tau);
+/* On a batch in coop mode (context option "coop": one large QP on many workgroups; Schur mode, dense factor) the six factor operations above --
+ * qpg_ldlchol, qpg_ldlcholQAtsigmaA, the three updates (unless "coop_updates" = 0) and qpg_ldlsolveLD_neg_dphi -- run on the grid kernels, through
+ * the launch chains a solve in coop mode uses; every other operation, and every other batch, runs on the QP's own workgroup.  `count`: how many
+ * single operations of this batch have run on the grid since it was created (0 on a batch that is not in coop mode). */
+int qpg_batch_coop_op_chains(qpg_batch *bt, qpg_int *count);
 /* ---- the KKT operations of solver_interface.h (batches created with factorization_method = FACTORIZE_KKT; QPG_ERR_UNSUPPORTED
  * otherwise).  State as in the reference: active_constraints, enter / leave lists with nb_enter / nb_leave, sigma_inv, gamma,
  * dphi; the (n+m) x (n+m) panel and sol_kkt / rhs_kkt live on the device ("L", "Dfac", "sol_kkt", "kkt_state").  With the context option

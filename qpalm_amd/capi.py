@@ -156,6 +156,8 @@ def load(path=None):
     if hasattr(L, "qpg_batch_adjoint_multi_device"):   # (absent from older builds of the library that tools/evidence/multi_direction_timing.py compares with)
         L.qpg_batch_adjoint_multi_device.argtypes = [C.c_void_p, C.POINTER(DeviceAdjoint), c_int, C.POINTER(DevicePoint), C.c_void_p, pi]
         L.qpg_batch_tangent_multi_device.argtypes = [C.c_void_p, C.POINTER(DeviceTangent), c_int, C.POINTER(DevicePoint), C.c_void_p, pi]
+    if hasattr(L, "qpg_batch_coop_op_chains"):   # (absent from older builds of the library that the tools/evidence scripts compare with)
+        L.qpg_batch_coop_op_chains.argtypes = [C.c_void_p, pi]
     L.qpg_batch_get_info.argtypes = [C.c_void_p, c_int, C.POINTER(Info)]
     L.qpg_batch_get_stats.argtypes = [C.c_void_p, c_int, C.POINTER(Stats)]
     L.qpg_batch_get_info_all.argtypes = [C.c_void_p, C.POINTER(Info)]
@@ -212,7 +214,7 @@ SYMBOLS = [
     "qpg_batch_step_subset_device", "qpg_batch_adjoint_subset_device", "qpg_batch_tangent_subset_device", "qpg_batch_polish_subset_device",
     "qpg_batch_set_sens_penalty", "qpg_batch_get_sens_penalty",
     "qpg_batch_get_active_device", "qpg_batch_get_active_subset_device", "qpg_batch_adjoint_at_device", "qpg_batch_tangent_at_device",
-    "qpg_batch_adjoint_multi_device", "qpg_batch_tangent_multi_device",
+    "qpg_batch_adjoint_multi_device", "qpg_batch_tangent_multi_device", "qpg_batch_coop_op_chains",
 ]
 
 

@@ -197,6 +197,7 @@ struct qpg_batch {
   std::string co_sig;
   long co_replays; /* graph launches of the last solve (QPALM_COOP_PROFILE prints it) */
   long co_sweeps;  /* persistent-sweep launches of the last solve (coop_test_kill counts them) */
+  long co_op_chains = 0; /* single operations of the boundary that ran on the grid kernels (run_op_coop; qpg_batch_coop_op_chains) */
   /* qpg_batch_update_Q_A: entry k of the device's A / Q values of a member = entry map[k] of the arrays its caller passed to qpg_batch_set_problem*
    * (take_column sorts a column's rows, Q keeps rows >= column).  An empty map = the same order (sorted columns, no upper entry of Q: the usual input).
    * The maps go to the device at the first update that needs one (val_maps_d: [B][nnzA] + [B][nnzQ] positions + [B][2] "same order" flags). */
@@ -1315,6 +1316,8 @@ template <class F> static void co_chain(qpg_batch *bt, int key, F issue) {
   bt->co_replays++;
   RT_GRAPH_LAUNCH(g.exec);
 }
+/* workgroups per launch of a member's chain: the members' chains run side by side (coop_solve) */
+static int coop_grid(const qpg_batch *bt) { return std::max(8, std::min(bt->ctx->coop_workgroups, 1024 / std::max(1, bt->B))); }
 static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qpg_scalars &sc) {
   if (bt->sparse) { /* sparse coop mode: the member's plan, launch by launch (chains 0 / 1: the factorisation into the factor / LD_Q, 2: the solve) */
     const qpg_batch::SpPlan &P = bt->sp_plan[(size_t)b];
@@ -1342,7 +1345,7 @@ static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qp
     return 0;
   }
   const int n = bt->probs[b].n, NB = 32, slot = b;
-  const int G = std::max(8, std::min(bt->ctx->coop_workgroups, 1024 / std::max(1, bt->B))); /* the members' chains run side by side (coop_solve) */
+  const int G = coop_grid(bt);
   /* FactorLds + FactorStage / SolveLds: below 48 KB, so that no launch needs a function-attribute call */
   const size_t lds_factor = ((sizeof(QP_INST(qp512, FactorLds)) + 15) & ~(size_t)15) + sizeof(QP_INST(qp512, FactorStage)) + 64, lds_solve = sizeof(QP_INST(qp512, CoSolveLds)) + 64;
   auto grid_for = [&](long units) { return (int)std::max<long>(1, std::min<long>(G, units)); };
@@ -1392,8 +1395,11 @@ static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qp
   return 0;
 }
 static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V, int budget, int dynamic, float *ms, int subset);
-static int coop_solve(qpg_batch *bt) {
-  qpg_view V = bt->V;
+/* the view a coop batch's kernels run with -- the iteration kernel that suspends, the chains of coop_linear_algebra -- for a whole solve (coop_solve)
+ * and for a single operation of the boundary (run_op_coop): where the iteration suspends, the refactorise-or-update rule, and the tables + counter
+ * words of the persistent sweep (allocated and cleared at first use) */
+static int coop_view(qpg_batch *bt, qpg_view &V) {
+  V = bt->V;
   V.offload = bt->sparse ? 1 : (bt->ctx->coop_updates ? 2 : 1); /* sparse coop mode: path updates stay on the QP's workgroup, and so does the one-workgroup path's refactorise-or-update rule */
   /* refactorise-or-update: an update_rank_threshold the user set explicitly wins; else coop_rank_threshold (-2: by measured cost) */
   if (!bt->sparse)
@@ -1408,6 +1414,11 @@ static int coop_solve(qpg_batch *bt) {
     }
     V.co_flags = (int32_t *)bt->co_tab_d; V.co_tab = (double *)((char *)bt->co_tab_d + flag_bytes); V.co_tab_stride = (int64_t)stride;
   }
+  return QPG_OK;
+}
+static int coop_solve(qpg_batch *bt) {
+  qpg_view V;
+  { const int rc = coop_view(bt, V); if (rc != QPG_OK) return rc; }
   std::vector<qpg_scalars> sc(bt->B);
   auto t0 = std::chrono::steady_clock::now();
   bt->co_replays = 0; bt->co_sweeps = 0;
@@ -2235,11 +2246,65 @@ static int run_op(qpg_batch *bt, qpg_int idx, int op, const char *fn) {
   }
   if (bt->sparse && op != QP_OP_MATVEC_A && op != QP_OP_MATVEC_Q && op != QP_OP_MATTVEC_A && op != QP_OP_RESIDUALS && op != QP_OP_ACTIVE && op != QP_OP_LINESEARCH)
     return fail(QPG_ERR_UNSUPPORTED, std::string(fn) + ": works on the dense panel (this batch keeps a sparse L D L')");
-  if (rpt <= 1) BT_LAUNCH(bt, k_op<1>, 1, shm, bt->V, (int)idx, op);
-  else if (rpt <= 2) BT_LAUNCH(bt, k_op<2>, 1, shm, bt->V, (int)idx, op);
-  else if (rpt <= 4) BT_LAUNCH(bt, k_op<4>, 1, shm, bt->V, (int)idx, op);
-  else BT_LAUNCH(bt, k_op<0>, 1, shm, bt->V, (int)idx, op);
+  auto own = [&](int o) { /* the operation on the QP's own workgroup */
+    if (rpt <= 1) BT_LAUNCH(bt, k_op<1>, 1, shm, bt->V, (int)idx, o);
+    else if (rpt <= 2) BT_LAUNCH(bt, k_op<2>, 1, shm, bt->V, (int)idx, o);
+    else if (rpt <= 4) BT_LAUNCH(bt, k_op<4>, 1, shm, bt->V, (int)idx, o);
+    else BT_LAUNCH(bt, k_op<0>, 1, shm, bt->V, (int)idx, o);
+  };
+  const bool factor_op = op == QP_OP_LDLCHOL || op == QP_OP_LDLCHOL_QATSA || op == QP_OP_SOLVE;
+  const bool update_op = op == QP_OP_UPDATE_ENTER || op == QP_OP_DOWNDATE_LEAVE || op == QP_OP_UPDATE_SIGMA;
+  if ((factor_op || (update_op && bt->ctx->coop_updates != 0)) && coop_wanted(bt)) {
+    /* A coop batch (Schur mode, dense factor, 512-thread instance: coop_wanted): the factor operations run on the grid kernels, through the chain
+     * a suspended iteration gets (coop_linear_algebra).  The chain's kernels read what they do from the member's scalars: pend_la / pend_gam /
+     * pend_nchange and the two rank counts are written for the call and put back after it; pend_stage stays 0, so that a later iterate or solve
+     * finds no suspension.  coop_updates = 0 keeps the updates on the QP's workgroup, as a solve does. */
+    qpg_view V;
+    { const int rc = coop_view(bt, V); if (rc != QPG_OK) return rc; }
+    if (op == QP_OP_UPDATE_SIGMA) own(QP_OP_SIGMA_SCALE); /* dev_solve's order around its la == 4 suspension: scale, sweeps, post */
+    if (op == QP_OP_SOLVE) own(QP_OP_NEG_DPHI);
+    qpg_scalars s0;
+    RT_MEMCPY_D2H(&s0, bt->V.sc + idx, sizeof(s0)); /* (the copy waits for the kernel before it) */
+    if (RT_STICKY()) return api_ok();
+    qpg_scalars s = s0;
+    s.pend_stage = 0; s.pend_action = 0; s.pend_kind = (op == QP_OP_SOLVE) ? 0 : 1; s.pend_nchange = 0; s.pend_gam = s0.gamma;
+    switch (op) {
+      case QP_OP_LDLCHOL: s.pend_la = 3; break;
+      case QP_OP_LDLCHOL_QATSA: s.pend_la = 1; break;
+      case QP_OP_UPDATE_ENTER: s.pend_la = 2; s.nb_leave = 0; break; /* (the one-workgroup operation passes 0 for the other count) */
+      case QP_OP_DOWNDATE_LEAVE: s.pend_la = 2; s.nb_enter = 0; break;
+      case QP_OP_UPDATE_SIGMA: s.pend_la = 4; s.pend_nchange = s0.nb_sigma_changed; break;
+      default: s.pend_la = 0; break; /* QP_OP_SOLVE: the solve chain alone */
+    }
+    RT_MEMCPY_H2D(bt->V.sc + idx, &s, sizeof(s));
+    coop_linear_algebra(bt, V, (int)idx, s);
+    bt->co_op_chains++;
+    const int rc_sync = RT_SYNC();
+    qpg_scalars s1; /* the kernels' counters stay, the fields written for the call go back */
+    RT_MEMCPY_D2H(&s1, bt->V.sc + idx, sizeof(s1));
+    s1.pend_stage = s0.pend_stage; s1.pend_la = s0.pend_la; s1.pend_action = s0.pend_action; s1.pend_kind = s0.pend_kind;
+    s1.pend_nchange = s0.pend_nchange; s1.pend_gam = s0.pend_gam; s1.nb_enter = s0.nb_enter; s1.nb_leave = s0.nb_leave;
+    RT_MEMCPY_H2D(bt->V.sc + idx, &s1, sizeof(s1));
+    if (rc_sync != 0) return fail(QPG_ERR_RUNTIME, std::string(fn) + " failed (coop kernels): " + RT_LAST_ERROR());
+    if (update_op && V.co_flags) { /* a workgroup of the one-launch sweep that gave up waiting: nobody resumes after a single operation to rebuild the factor */
+      int fl[4];
+      RT_MEMCPY_D2H(fl, V.co_flags + (size_t)idx * 4, sizeof(fl));
+      if (fl[1] != 0) {
+        RT_MEMSET(V.co_flags + (size_t)idx * 4, 0, sizeof(fl));
+        return fail(QPG_ERR_RUNTIME, std::string(fn) + ": coop update sweep: workgroup " + std::to_string(fl[1] - 1) + " timed out waiting for a table (the factor is half updated)");
+      }
+    }
+    if (op != QP_OP_UPDATE_SIGMA) return api_ok();
+    op = QP_OP_SIGMA_POST;
+  }
+  own(op);
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, std::string(fn) + " failed: " + RT_LAST_ERROR());
+  return api_ok();
+}
+/* single operations of the boundary that ran on the coop grid kernels since the batch was created (run_op; 0 on a batch that is not in coop mode) */
+extern "C" int qpg_batch_coop_op_chains(qpg_batch *bt, qpg_int *count) {
+  NEED_SETUP(bt, "qpg_batch_coop_op_chains");
+  if (count) *count = (qpg_int)bt->co_op_chains;
   return api_ok();
 }
 static int matvec_common(qpg_batch *bt, qpg_int idx, int op, size_t nin, size_t nout, const qpg_float *x, qpg_float *y, const char *fn) {

@@ -1961,7 +1961,10 @@ QPNI void dense_updown_big(const int *Atp_, const int *Ati_, const double *Atss_
  * buffers.  State of one update, in the slot's stash area of Wst (hst = Wst + K n + QPG_DUMMY):
  *   hst[0..2K)  1/alpha: buffer (J / 32) & 1 is read, the other written             hst[CO_UD_JMIN] first nonzero row
  *   hst[CO_UD_STAGED] block column held by the stage (-1 none)    hst[CO_UD_D ..) 32 pivots    hst[CO_UD_L ..) 32 x 32 entries
- * The arithmetic per entry is dense_updown_big's, so the factor is bit-identical to the one-workgroup sweep's.
+ * The arithmetic per entry is dense_updown_big's, so the factor is bit-identical to the one-workgroup sweep's wherever that sweep takes its
+ * ranks 16 at a time too: dense_updown_big, and dense_updown with one or two rows per thread.  With three or four rows per thread
+ * dense_updown takes 8 ranks per sweep (QP_KSEL): the prefix tree of a column's pivots (qp_rank_pivots) then sums other groups of ranks and
+ * the factors differ in the last bits (tests/test_coop_ops_exact.py: sweeps_alike).
  * ------------------------------------------------------------------------------------------- */
 #define CO_UD_JMIN 100
 #define CO_UD_STAGED 101

@@ -34,6 +34,10 @@
 #define QP_OP_KKT_LEAVE 17
 #define QP_OP_KKT_SOLVE 18
 #define QP_OP_KKT_EXPAND 19 /* a compact KKT factor spread out to the full (n+m) layout (before the host reads it) */
+/* the steps of QP_OP_UPDATE_SIGMA and QP_OP_SOLVE that stay on the QP's workgroup when the operation itself runs on the coop grid kernels (run_op_coop) */
+#define QP_OP_SIGMA_SCALE 20
+#define QP_OP_SIGMA_POST 21
+#define QP_OP_NEG_DPHI 22
 
 /* qpalm_setup's device part: Ruiz scaling (scaling.c:34-113) and derived copies.
  * mode 0: fresh setup (nscale iterations); mode 1: qpalm_update_settings with more scaling
@@ -624,6 +628,10 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_op(qpg_view V, int b, int
     case QP_OP_KKT_LEAVE: if (V.kkt) kkt_newton<RPT>(&V, b, L, Dg, Wst, &I, lds, 2, 0, I.s.nb_leave, 0); break;
     case QP_OP_KKT_SOLVE: if (V.kkt) kkt_newton<RPT>(&V, b, L, Dg, Wst, &I, lds, 0, 0, 0, QP_KKT_SOLVE); break;
     case QP_OP_KKT_EXPAND: if (V.kkt) kkt_newton<RPT>(&V, b, L, Dg, Wst, &I, lds, 5, 0, 0, 0); break;
+    /* coop mode: QP_OP_UPDATE_SIGMA's two halves around the grid's sweeps, QP_OP_SOLVE's right-hand side in front of the grid's solve */
+    case QP_OP_SIGMA_SCALE: dev_ldlupdate_sigma_scale(a, I.s.nb_sigma_changed); break;
+    case QP_OP_SIGMA_POST: dev_update_sigma_post(a, I, I.s.nb_sigma_changed); break;
+    case QP_OP_NEG_DPHI: for (int j = tid; j < n; j += QP_T) a.d()[j] = a.dphi()[j] * -1; break;
     default: break;
   }
   __syncthreads();

@@ -729,6 +729,13 @@ class QpalmBatch:
     def op(self, name, b=0):
         self._check(getattr(self.L, "qpg_" + name)(self.h, int(b)))
 
+    def coop_op_chains(self):
+        """how many single operations of this batch (op: ldlchol, ldlcholQAtsigmaA, the three updates, ldlsolveLD_neg_dphi) have run on the coop
+        grid kernels since it was created; 0 on a batch that is not in coop mode"""
+        c = capi.c_int(0)
+        self._check(self.L.qpg_batch_coop_op_chains(self.h, C.byref(c)))
+        return int(c.value)
+
     def exact_linesearch(self, b=0):
         t = capi.c_float(0.0)
         self._check(self.L.qpg_exact_linesearch(self.h, int(b), C.byref(t)))

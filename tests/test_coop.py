@@ -6,8 +6,10 @@ launch per 64-column block), qpalm_capi.inc: coop_solve.  Reference: src/solver_
 calls), src/nonconvex.c:29-168 for config 5's front-end.
 
 Parity: against the one-workgroup engine (same statuses, iteration counts and refactorise / rank-update split, x, y to 1e-9; the
-factorisation, the updates and the forward substitution are bit-identical per entry, the backward substitution sums in another
-order) and against the oracle."""
+factorisation, the updates -- where the one-workgroup sweep takes 16 ranks at a time like the grid's, not 8 -- and the forward
+substitution are bit-identical per entry, the backward substitution sums in another order) and against the oracle.  The bit-identity statements themselves -- L and D of the grid kernels against the one-workgroup
+kernels', the one-launch sweep against the chain of launches, operation by operation at the block edges -- are asserted in
+tests/test_coop_ops_exact.py."""
 import time
 
 import os

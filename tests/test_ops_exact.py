@@ -151,7 +151,9 @@ def cases(lst):
 
 
 class Opened:
-    """the common set-up: one QP, scaling = 0, begin_solve, iterate(2); the batch is closed and every context option restored on exit"""
+    """the common set-up: one QP, scaling = 0, begin_solve, iterate(2); the batch is closed and every context option restored on exit.
+    options: context options for the batch, e.g. sweep_ranks, linesearch_hbm, narrow_rows, and coop / coop_updates / coop_workgroups / coop_graphs
+    (tests/test_coop_ops_exact.py: the same operations on the grid kernels)"""
 
     def __init__(self, ctx, case, seed=None, **options):
         self.ctx, self.case, self.options = ctx, case, options
@@ -185,6 +187,10 @@ class Opened:
             ctx.set_option("sweep_ranks", 16)
             ctx.set_option("linesearch_hbm", 0)
             ctx.set_option("narrow_rows", 1)
+            ctx.set_option("coop", 0)
+            ctx.set_option("coop_updates", 2)
+            ctx.set_option("coop_graphs", 1)
+            ctx.set_option("coop_workgroups", 3 if ctx.kind == "emu" else 256)     # what the ctx fixture sets (tests/conftest.py)
         return False
 
     # -- the sets of rows the tests use ---------------------------------------------------------------------------------------
@@ -209,9 +215,9 @@ class Opened:
         act[np.asarray(rows_in, dtype=np.int64)] = 1
         self.bt.set_ivec("active", act)
 
-    def factor_of(self, rows_in):
+    def factor_of(self, rows_in, op="ldlcholQAtsigmaA"):
         self.set_active(rows_in)
-        self.bt.op("ldlcholQAtsigmaA")
+        self.bt.op(op)
         return self.bt.factor(0)
 
     def update_vectors(self, rows):
@@ -253,10 +259,12 @@ def product_error(L, D, H, cols):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. factor
-def _check_factor(o):
+def _check_factor(o, rows_in=None, op="ldlcholQAtsigmaA"):
+    """rows_in = None: every second ordinary row and every special row; op = "ldlchol" factorises Q + I / gamma alone (rows_in = [])"""
     n = o.case.n
-    rows_in = o.base_active() + o.special_rows()
-    L, D = o.factor_of(rows_in)
+    if rows_in is None:
+        rows_in = o.base_active() + o.special_rows()
+    L, D = o.factor_of(rows_in, op)
     assert np.all(np.isfinite(L)) and np.all(np.isfinite(D))
     H = o.H(rows_in)
     check_conditioning(H)
@@ -269,6 +277,7 @@ def _check_factor(o):
     ratio = worst_ratio(R, bound)
     print("factor %s: max |R| / bound = %.3g, r = %d" % (o.case.id, ratio, r))
     assert ratio <= 1.0, (o.case.id, ratio)
+    return L, D
 
 
 @cases(TABLE)
@@ -286,9 +295,9 @@ def test_factor_narrow_rows(ctx, case, narrow):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. update / downdate
-def _updown(o, start_rows, change_rows, sign):
-    """(kernel's error, reference's error, floor n u max|H_0|, L, D): `change_rows` enter (sign = +1) or leave (-1) the factor of `start_rows`"""
-    n, bt = o.case.n, o.bt
+def _run_updown(o, start_rows, change_rows, sign):
+    """(L0, D0, L, D, new rows): the factor of `start_rows`, and after `change_rows` have entered (sign = +1) or left (-1) it"""
+    bt = o.bt
     L0, D0 = o.factor_of(start_rows)
     if sign > 0:
         bt.set_ivec("enter", change_rows); bt.set_scalar("nb_enter", len(change_rows)); bt.set_scalar("nb_leave", 0)
@@ -299,15 +308,28 @@ def _updown(o, start_rows, change_rows, sign):
         bt.op("ldldowndate_leaving_constraints")
         new_rows = [i for i in start_rows if i not in set(change_rows)]
     L, D = bt.factor(0)
+    return L0, D0, L, D, new_rows
+
+
+def _updown_errors(o, L0, D0, L, D, H0, Hn, vectors, sign):
+    """(kernel's error, reference's error, floor n u max|H_0|) of a factor (L, D) meant to be that of Hn = H0 + sign sum w w' over the rows w of
+    `vectors`, reached from the factor (L0, D0) of H0: the reference applies the same vectors to (L0, D0) one rank at a time in fp64"""
+    n = o.case.n
     assert np.all(np.isfinite(L)) and np.all(np.isfinite(D))
-    H0, Hn = o.H(start_rows), o.H(new_rows)
     check_conditioning(H0)
     check_conditioning(Hn)
-    Lr, Dr = xr.sequential_updown(L0, D0, o.update_vectors(change_rows), sign)
+    Lr, Dr = xr.sequential_updown(L0, D0, vectors, sign)
     cols = sample_columns(n, 13)
     e_k = float(np.max(np.abs(product_error(L, D, Hn, cols))))
     e_r = float(np.max(np.abs(product_error(Lr, Dr, Hn, cols))))
     floor = n * xr.U * float(np.max(np.abs(H0)))
+    return e_k, e_r, floor
+
+
+def _updown(o, start_rows, change_rows, sign):
+    """(kernel's error, reference's error, floor n u max|H_0|, L, D): `change_rows` enter (sign = +1) or leave (-1) the factor of `start_rows`"""
+    L0, D0, L, D, new_rows = _run_updown(o, start_rows, change_rows, sign)
+    e_k, e_r, floor = _updown_errors(o, L0, D0, L, D, o.H(start_rows), o.H(new_rows), o.update_vectors(change_rows), sign)
     return e_k, e_r, floor, L, D
 
 
@@ -353,26 +375,41 @@ def test_update_33_rows_enter_32_ranks(ctx, case):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. solve
+class SolveJudge:
+    """|L D L' d + dphi| <= 3 gamma_n |L||D||L'||d| for the factor (L, D) as read back"""
+
+    def __init__(self, case, L, D):
+        self.case = case
+        Lu = xr.unit_lower(L)
+        self.Ll, self.Dl = np.asarray(Lu, dtype=xr.LD), np.asarray(D, dtype=xr.LD)
+        self.La, self.Da = np.abs(Lu), np.abs(D)
+
+    def check(self, d, rhs, name):
+        n, Ll, Dl, La, Da = self.case.n, self.Ll, self.Dl, self.La, self.Da
+        assert np.all(np.isfinite(d))
+        dl = np.asarray(d, dtype=xr.LD)
+        res = np.abs(Ll @ (Dl * (Ll.T @ dl)) + np.asarray(rhs, dtype=xr.LD))
+        bound = 3 * xr.gamma_k(n) * (La @ (Da * (La.T @ np.abs(d))))
+        ratio = worst_ratio(res, bound)
+        print("solve %s, rhs %s: max residual / bound = %.3g" % (self.case.id, name, ratio))
+        assert ratio <= 1.0, (self.case.id, name, ratio)
+
+
+def solve_rhs(n):
+    ends = np.zeros(n); ends[0] += 1.0; ends[n - 1] += 1.0
+    return (("random", np.random.default_rng(500 + n).standard_normal(n)), ("e_0 + e_{n-1}", ends))
+
+
 @cases(TABLE)
 def test_solve(ctx, case):
     with Opened(ctx, case) as o:
         n, bt = case.n, o.bt
         L, D = o.factor_of(o.base_active() + o.special_rows())
-        Lu = xr.unit_lower(L)
-        Ll, Dl = np.asarray(Lu, dtype=xr.LD), np.asarray(D, dtype=xr.LD)
-        La, Da = np.abs(Lu), np.abs(D)
-        ends = np.zeros(n); ends[0] += 1.0; ends[n - 1] += 1.0
-        for name, rhs in (("random", np.random.default_rng(500 + n).standard_normal(n)), ("e_0 + e_{n-1}", ends)):
+        judge = SolveJudge(case, L, D)
+        for name, rhs in solve_rhs(n):
             bt.set_vec("dphi", rhs)
             bt.op("ldlsolveLD_neg_dphi")
-            d = bt.vec("d")
-            assert np.all(np.isfinite(d))
-            dl = np.asarray(d, dtype=xr.LD)
-            res = np.abs(Ll @ (Dl * (Ll.T @ dl)) + np.asarray(rhs, dtype=xr.LD))
-            bound = 3 * xr.gamma_k(n) * (La @ (Da * (La.T @ np.abs(d))))
-            ratio = worst_ratio(res, bound)
-            print("solve %s, rhs %s: max residual / bound = %.3g" % (case.id, name, ratio))
-            assert ratio <= 1.0, (case.id, name, ratio)
+            judge.check(bt.vec("d"), rhs, name)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 4. SpMV
