@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "lib", "libqpalm_gfx950.so")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libqpalm_gfx950_emu.so")
 _SRCS = ["../host/qpalm_host.c", "../host/qpalm_qps.c", "qpalm_kkt.h", "qpalm_sparse.h", "qpalm_sparse_kkt.h", "qpalm_adjoint.h", "qpalm_gfx950.hip", "qpalm_kernels.h", "qpalm_device.h", "qpalm_dense.h", "qpalm_iter.h", "qpalm_types.h",
-         "qpalm_capi.inc"]
+         "qpalm_capi.inc", "qpalm_host_convert.h", "qpalm_host_symbolic.h"]
 
 
 def _stale(target, deps):

@@ -3,9 +3,10 @@
  * qpalm_gfx950.hip (the shipped HIP build) and by tests/emu/qpalm_emu.cpp (kernel-source emulation,
  * test-only); both define the RT_* runtime macros first.
  *
- * Host work is limited to what the reference's host does around the path: validation
- * (src/validate.c), data copies / format conversion (qpalm_setup's deep copies, src/qpalm.c:128-144;
- * the A' pattern that cholmod_transpose builds in iteration.c:81), and launching kernels.
+ * Host work is what the reference's host does around the path: validation (src/validate.c) and data copies / format conversion
+ * (qpalm_setup's deep copies, src/qpalm.c:128-144; the A' pattern that cholmod_transpose builds in iteration.c:81), both in
+ * qpalm_host_convert.h; the symbolic analysis of the sparse factors (what cholmod_analyze does; with the nested dissection and the launch
+ * plans of sparse coop mode in qpalm_host_symbolic.h); and, here, the batch's memory and launching kernels.
  */
 #include <math.h>
 #include <stdio.h>
@@ -22,6 +23,8 @@
 #include <map>
 
 #include "../../include/qpalm_gfx950.h"
+#include "qpalm_host_convert.h"
+#include "qpalm_host_symbolic.h"
 
 /* The HIP build holds two instances of the kernels (namespaces qp512 / qp256, see qpalm_gfx950.hip); the emulation build
  * (tests) holds one, in the global namespace.  BT_LAUNCH picks the instance of a batch. */
@@ -46,6 +49,15 @@
     if ((bt)->small == 2) RT_TIMED_LAUNCH(ms, QP_INST(qp128, kern), grid, QP_T_TINY, shmem, __VA_ARGS__);   \
     else if ((bt)->small) RT_TIMED_LAUNCH(ms, QP_INST(qp256, kern), grid, QP_T_SMALL, shmem, __VA_ARGS__);  \
     else RT_TIMED_LAUNCH(ms, QP_INST(qp512, kern), grid, QP_T, shmem, __VA_ARGS__);                         \
+  } while (0)
+/* A kernel template over the dense factor's rows per thread (rpt): up to 4 the update sweep keeps its running vectors in registers (kern<1|2|4>), larger
+ * factors use the large-factor sweep with the vectors in HBM (kern<0>).  BT_RPT(rpt, R, BT_LAUNCH(bt, kern<R>, grid, ...)) launches that instance. */
+#define BT_RPT(rpt, R, ...)                                                                                 \
+  do {                                                                                                      \
+    if ((rpt) <= 1) { constexpr int R = 1; __VA_ARGS__; }                                                   \
+    else if ((rpt) <= 2) { constexpr int R = 2; __VA_ARGS__; }                                              \
+    else if ((rpt) <= 4) { constexpr int R = 4; __VA_ARGS__; }                                              \
+    else { constexpr int R = 0; __VA_ARGS__; }                                                              \
   } while (0)
 
 static thread_local std::string g_err;
@@ -154,13 +166,7 @@ struct qpg_ctx {
  * The slab is anonymous memory with transparent huge pages requested: first-touching 5.8 GB of 4 KB pages (the benchmark batch)
  * costs 0.55 s whatever the number of threads -- the kernel serialises the faults -- against 0.03-0.06 s with 2 MB pages, and the
  * runtime copies from such memory at 44-56 GB/s, the rate of page-locked memory, whose allocation alone would cost 1.2 s
- * (tools/evidence/host_alloc_probe.hip, profiles/r04/setup/). */
-enum { H_AP, H_AI, H_ATP, H_ATI, H_ATPERM, H_AINV, H_QP, H_QI, H_QFP, H_QFI, H_QFPERM, H_AX, H_QX, H_Q, H_BMIN, H_BMAX, H_COUNT };
-struct HostProblem { /* one member: its own dimensions (<= the batch's) and entry counts; the arrays live in the slab */
-  int n, m, nzA, nzQ, nzQf;
-  double c;
-  bool set;
-};
+ * (tools/evidence/host_alloc_probe.hip, profiles/r04/setup/).  The arrays (H_*) and HostProblem: qpalm_host_convert.h. */
 
 struct qpg_batch {
   qpg_ctx *ctx;
@@ -181,11 +187,7 @@ struct qpg_batch {
   void *sparse_d; size_t sparse_d_bytes; /* symbolic arrays of every member + values / work vectors of every slot */
   std::vector<long long> sp_nnz; /* nnz(L) of every member (qpg_batch_sparse_info) */
   std::vector<int> sp_levels, sp_perm; /* height of every member's elimination tree; [B][n] ordering of its factor (qpg_batch_sparse_perm) */
-  /* sparse coop mode: every member's launch plan (sparse_coop_plan; empty: the batch runs on one workgroup per QP).  A launch covers the levels
-   * [lev0, lev1) of the elimination tree on `grid` workgroups: more than one level only with grid = 1 */
-  struct SpLaunch { int lev0, lev1, grid; };
-  struct SpPlan { std::vector<SpLaunch> factor, solve; int vec_grid, solve_launches, max_grid; }; /* vec_grid: workgroups of the solve's elementwise launches */
-  std::vector<SpPlan> sp_plan;
+  std::vector<SpPlan> sp_plan; /* sparse coop mode: every member's launch plan (sparse_coop_plan; empty: the batch runs on one workgroup per QP) */
   qpg_view V;
   bool is_setup;
   float last_solve_ms;
@@ -417,121 +419,12 @@ static int set_problem_impl(qpg_batch *bt, qpg_int idx, qpg_int n_, qpg_int m_, 
                             const qpg_int *Ap, const qpg_int *Ai, const qpg_float *Ax, const qpg_float *q,
                             qpg_float c, const qpg_float *bmin, const qpg_float *bmax) {
   if (idx < 0 || idx >= bt->B) return fail(QPG_ERR_INVALID, "qpg_batch_set_problem: bad index");
-  const int n = (int)n_, m = (int)m_;
-  if (!Qp || !Ap || !q || (m && (!bmin || !bmax))) return fail(QPG_ERR_INVALID, "Missing data");
-  for (int j = 0; j < m; j++)
-    if (bmin[j] > bmax[j]) { /* validate_data, src/validate.c:31-39 */
-      char buf[160]; snprintf(buf, sizeof buf, "Lower bound at index %d is greater than upper bound: %.4e > %.4e", j, bmin[j], bmax[j]);
-      return fail(QPG_ERR_INVALID, buf);
-    }
-  const qpg_int nzA = Ap[n], nzQ = Qp[n];
-  if (Ap[0] != 0 || Qp[0] != 0) return fail(QPG_ERR_INVALID, "qpg_batch_set_problem: column pointers must start at 0"); /* (entries before Ap[0] of the reused slab would be stale: ADVICE round 4) */
-  if (nzA < 0 || nzQ < 0 || nzA > bt->nnzA || nzQ > bt->nnzQ) return fail(QPG_ERR_INVALID, "qpg_batch_set_problem: more nonzeros than nnzA_max / nnzQ_max");
-  HostProblem &P = bt->probs[idx];
-  P.n = n; P.m = m; P.set = false;
   const size_t ib = (size_t)idx;
-  int *hAp = bt->harr<int>(H_AP, ib), *hAi = bt->harr<int>(H_AI, ib), *hAtp = bt->harr<int>(H_ATP, ib), *hAti = bt->harr<int>(H_ATI, ib);
-  int *hAtperm = bt->harr<int>(H_ATPERM, ib), *hAinv = bt->harr<int>(H_AINV, ib), *hQp = bt->harr<int>(H_QP, ib), *hQi = bt->harr<int>(H_QI, ib);
-  int *hQfp = bt->harr<int>(H_QFP, ib), *hQfi = bt->harr<int>(H_QFI, ib), *hQfperm = bt->harr<int>(H_QFPERM, ib);
-  double *hAx = bt->harr<double>(H_AX, ib), *hQx = bt->harr<double>(H_QX, ib);
-  /* the member's entries, then padding up to the batch's stride: zeros, or (column pointers of a smaller member) the last value
-   * repeated = empty columns */
-  auto pad = [](auto *d, size_t used, size_t stride) { if (used < stride) memset(d + used, 0, (stride - used) * sizeof(*d)); };
-  auto pad_ptr = [](int *d, size_t used, size_t stride) { for (size_t j = used; j < stride; j++) d[j] = d[used - 1]; };
-  /* One column of a CSC matrix (entries k0 .. k1-1 of the caller's arrays, optionally only rows >= rmin) into dst at position pos,
-   * rows ascending: already-sorted columns (the usual case) are copied straight, others sorted by row (stable: equal rows keep
-   * the caller's order, QPS-loaded matrices may be unsorted, SURVEY App. F).  Returns the new position, -1 on a bad index. */
-  std::vector<std::pair<int, double> > tmp;
-  bool reordered = false; /* some column was sorted or lost an entry: the device's order of the values is not the caller's (value_map below) */
-  auto take_column = [&tmp, &reordered](const qpg_int *I, const qpg_float *X, qpg_int k0, qpg_int k1, qpg_int rmin, qpg_int rmax, int *di, double *dx, qpg_int pos) -> qpg_int {
-    bool sorted = true;
-    qpg_int prev = -1;
-    const qpg_int p0 = pos;
-    for (qpg_int k = k0; k < k1; k++) {
-      const qpg_int r = I[k];
-      if (r < 0 || r >= rmax) return -1;
-      if (r < rmin) { reordered = true; continue; }
-      if (r < prev) sorted = false;
-      prev = r;
-      di[pos] = (int)r; dx[pos] = X[k]; pos++;
-    }
-    if (!sorted) {
-      reordered = true;
-      tmp.clear();
-      for (qpg_int t = p0; t < pos; t++) tmp.push_back(std::make_pair(di[t], dx[t]));
-      std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
-      for (qpg_int t = p0; t < pos; t++) { di[t] = tmp[t - p0].first; dx[t] = tmp[t - p0].second; }
-    }
-    return pos;
-  };
-  /* position in the caller's arrays of every entry take_column keeps, in its order (the same stable sort, on positions); only for input it reordered */
-  auto value_map = [n](const qpg_int *Pc, const qpg_int *I, bool lower, std::vector<int> &map) {
-    map.clear();
-    for (int j = 0; j < n; j++) {
-      const size_t p0 = map.size();
-      for (qpg_int k = Pc[j]; k < Pc[j + 1]; k++) if (!lower || I[k] >= j) map.push_back((int)k);
-      std::stable_sort(map.begin() + p0, map.end(), [I](int a, int b) { return I[a] < I[b]; });
-    }
-  };
-  /* A: CSC with sorted rows inside each column */
-  for (int j = 0; j < n; j++) {
-    if (Ap[j + 1] < Ap[j] || Ap[j] < 0 || Ap[j + 1] > nzA) return fail(QPG_ERR_INVALID, "A: column pointers not monotone");
-    hAp[j] = (int)Ap[j];
-    if (take_column(Ai, Ax, Ap[j], Ap[j + 1], 0, m, hAi, hAx, Ap[j]) < 0) return fail(QPG_ERR_INVALID, "A: row index out of range");
-  }
-  hAp[n] = (int)nzA;
-  bt->map_A[ib].clear();
-  if (reordered) value_map(Ap, Ai, false, bt->map_A[ib]);
-  reordered = false;
-  pad_ptr(hAp, (size_t)n + 1, bt->hper[H_AP]); pad(hAi, (size_t)nzA, bt->hper[H_AI]); pad(hAx, (size_t)nzA, bt->hper[H_AX]);
-  P.nzA = (int)nzA;
-  /* A' pattern (what cholmod_transpose(A,1) builds, iteration.c:81) + permutation into A */
-  {
-    std::vector<int> cnt(m + 1, 0);
-    for (qpg_int k = 0; k < nzA; k++) cnt[hAi[k] + 1]++;
-    for (int r = 0; r < m; r++) cnt[r + 1] += cnt[r];
-    for (int r = 0; r <= m; r++) hAtp[r] = cnt[r];
-    for (int j = 0; j < n; j++)
-      for (int k = hAp[j]; k < hAp[j + 1]; k++) { const int dst = cnt[hAi[k]]++; hAti[dst] = j; hAtperm[dst] = k; hAinv[k] = dst; }
-    pad_ptr(hAtp, (size_t)m + 1, bt->hper[H_ATP]);
-    pad(hAti, (size_t)nzA, bt->hper[H_ATI]); pad(hAtperm, (size_t)nzA, bt->hper[H_ATPERM]); pad(hAinv, (size_t)nzA, bt->hper[H_AINV]);
-  }
-  /* Q: keep the lower triangle only (stype = -1: upper entries are ignored, B6), sorted */
-  {
-    qpg_int pos = 0;
-    for (int j = 0; j < n; j++) {
-      if (Qp[j + 1] < Qp[j] || Qp[j] < 0 || Qp[j + 1] > nzQ) return fail(QPG_ERR_INVALID, "Q: column pointers not monotone");
-      hQp[j] = (int)pos;
-      pos = take_column(Qi, Qx, Qp[j], Qp[j + 1], j, n, hQi, hQx, pos);
-      if (pos < 0) return fail(QPG_ERR_INVALID, "Q: row index out of range");
-    }
-    hQp[n] = (int)pos;
-    P.nzQ = (int)pos;
-    bt->map_Q[ib].clear();
-    if (reordered) value_map(Qp, Qi, true, bt->map_Q[ib]);
-    pad_ptr(hQp, (size_t)n + 1, bt->hper[H_QP]); pad(hQi, (size_t)pos, bt->hper[H_QI]); pad(hQx, (size_t)pos, bt->hper[H_QX]);
-    /* both triangles, compressed by column (== by row), rows ascending, with the map into Q */
-    std::vector<int> cnt(n + 1, 0);
-    for (int j = 0; j < n; j++)
-      for (int k = hQp[j]; k < hQp[j + 1]; k++) { cnt[j + 1]++; if (hQi[k] != j) cnt[hQi[k] + 1]++; }
-    for (int j = 0; j < n; j++) cnt[j + 1] += cnt[j];
-    memcpy(hQfp, cnt.data(), ((size_t)n + 1) * sizeof(int));
-    P.nzQf = cnt[n];
-    std::vector<int> cur(cnt.begin(), cnt.end() - 1);
-    for (int j = 0; j < n; j++) /* upper parts: entry (i>j, j) is element (j, i) of column i */
-      for (int k = hQp[j]; k < hQp[j + 1]; k++) { const int i = hQi[k]; if (i != j) { const int dst = cur[i]++; hQfi[dst] = j; hQfperm[dst] = k; } }
-    for (int j = 0; j < n; j++)
-      for (int k = hQp[j]; k < hQp[j + 1]; k++) { const int dst = cur[j]++; hQfi[dst] = hQi[k]; hQfperm[dst] = k; }
-    pad_ptr(hQfp, (size_t)n + 1, bt->hper[H_QFP]); pad(hQfi, (size_t)cnt[n], bt->hper[H_QFI]); pad(hQfperm, (size_t)cnt[n], bt->hper[H_QFPERM]);
-  }
-  {
-    double *hq = bt->harr<double>(H_Q, ib), *hlo = bt->harr<double>(H_BMIN, ib), *hhi = bt->harr<double>(H_BMAX, ib);
-    memcpy(hq, q, (size_t)n * sizeof(double)); pad(hq, (size_t)n, bt->hper[H_Q]);
-    if (m) { memcpy(hlo, bmin, (size_t)m * sizeof(double)); memcpy(hhi, bmax, (size_t)m * sizeof(double)); }
-    pad(hlo, (size_t)m, bt->hper[H_BMIN]); pad(hhi, (size_t)m, bt->hper[H_BMAX]);
-  }
-  P.c = c; P.set = true;
-  return api_ok();
+  ConvertDst D;
+  for (int a = 0; a < H_COUNT; a++) { D.p[a] = bt->hslab + bt->hoff[a] + ib * bt->hper[a] * bt->helem[a]; D.stride[a] = bt->hper[a]; }
+  std::string msg;
+  const int rc = convert_problem(D, (int)n_, (int)m_, Qp, Qi, Qx, Ap, Ai, Ax, q, c, bmin, bmax, bt->probs[ib], bt->map_A[ib], bt->map_Q[ib], msg);
+  return rc ? fail(rc, msg) : api_ok();
 }
 
 /* qpalm_setup's host work for MANY QPs in one call (src/qpalm.c:128-144 deep copies + the A' pattern of iteration.c:81): members
@@ -662,225 +555,11 @@ static int arena_alloc(qpg_batch *bt) { /* runs on the thread qpg_batch_create s
   return 0;
 }
 
-/* ---- sparse factor: symbolic analysis (host, once per member) ------------------------------------------------------------------
- * Pattern of H = Q + A'A (+ diagonal) with ALL rows of A, natural ordering (solver_interface.c:530-540); elimination tree and the
- * pattern of L by the classic column recurrence  struct(L_j) = struct(H_j) u U_{children c of j} struct(L_c) \ {c},
- * parent(j) = min struct(L_j)  (Liu 1990; what cholmod_analyze computes for a simplicial factor); the same entries by rows; the level
- * sets of the tree (level = height above the leaves: the columns a column depends on are its descendants).  Everything int32. */
-struct SparseSym {
-  std::vector<int> Lp, Li, Rp, Rk, Rpos, levptr, levcol;
-  std::vector<int> perm, iperm; /* the factor is that of P H P': perm[new] = old, iperm[old] = new (identity: natural ordering) */
-  int nlev;
-  bool dissected;
-};
-/* Nested dissection (sparse_order, below) of the graph of H = Q + A'A or of K (sparse_adj_H / sparse_adj_K; George's automatic scheme on breadth-first level structures): a band-like pattern,
- * whose elimination tree under the natural ordering is a chain of n columns (one column per level: the factorisation and the solves
- * then run at the latency of n dependent steps), becomes a tree of height ~ leaf + separator x log2(n / leaf) whose levels hold
- * hundreds of independent columns.  Vertices of very high degree (dense rows / columns: an arrow's shaft) are set aside and ordered last;
- * the rest is split recursively: connected components one after the other; a component by the middle level of the level structure
- * rooted at a pseudo-peripheral vertex (first half, second half, separator last); small pieces keep their natural order.  The
- * reference configures CHOLMOD_NATURAL; this is an engine option that changes speed and rounding, not what is computed. */
-/* the graph a factor's ordering works on: neighbours of every vertex (original numbering, no self loops) */
-struct SparseAdj { std::vector<int> p, i; };
-/* graph of H = Q + A'A (a long row of A -- a clique of H whatever the ordering -- enters as a chain of its columns: ordering quality only) */
-static void sparse_adj_H(const qpg_batch *bt, size_t b, SparseAdj &G) {
+/* ---- sparse factor: the symbolic analysis (host, once per member) is qpalm_host_symbolic.h; this is the pattern it reads */
+static SparsePattern member_pattern(const qpg_batch *bt, size_t b) {
   const HostProblem &P = bt->probs[b];
-  const int n = P.n;
-  const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
-  const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
-  const int LONG_ROW = 64;
-  std::vector<int> &adjp = G.p, &adji = G.i, mark((size_t)n, -1);
-  adjp.assign((size_t)n + 1, 0); adji.clear();
-  for (int j = 0; j < n; j++) {
-    mark[j] = j;
-    for (int k = Qfp[j]; k < Qfp[j + 1]; k++) { const int i = Qfi[k]; if (mark[i] != j) { mark[i] = j; adji.push_back(i); } }
-    for (int p = Ap[j]; p < Ap[j + 1]; p++) {
-      const int t = Ai[p], q0 = Atp[t], q1 = Atp[t + 1];
-      if (q1 - q0 <= LONG_ROW) { for (int q = q0; q < q1; q++) { const int i = Ati[q]; if (mark[i] != j) { mark[i] = j; adji.push_back(i); } } }
-      else for (int q = q0; q < q1; q++) if (Ati[q] == j) { /* neighbours in the row's chain */
-        if (q > q0 && mark[Ati[q - 1]] != j) { mark[Ati[q - 1]] = j; adji.push_back(Ati[q - 1]); }
-        if (q + 1 < q1 && mark[Ati[q + 1]] != j) { mark[Ati[q + 1]] = j; adji.push_back(Ati[q + 1]); }
-      }
-    }
-    adjp[j + 1] = (int)adji.size();
-  }
-}
-/* graph of K_full = [[Q + I, A'], [A, I]] with ALL rows of A (the reference's kkt_full): vertices 0 .. n-1 the variables, n + k constraint k.
- * A superset of every active set's K, so the factor's structure never changes when rows enter or leave */
-static void sparse_adj_K(const qpg_batch *bt, size_t b, SparseAdj &G) {
-  const HostProblem &P = bt->probs[b];
-  const int n = P.n, m = P.m;
-  const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
-  const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
-  std::vector<int> &adjp = G.p, &adji = G.i, mark((size_t)n, -1);
-  adjp.assign((size_t)n + m + 1, 0); adji.clear();
-  for (int j = 0; j < n; j++) {
-    mark[j] = j;
-    for (int k = Qfp[j]; k < Qfp[j + 1]; k++) { const int i = Qfi[k]; if (mark[i] != j) { mark[i] = j; adji.push_back(i); } }
-    for (int p = Ap[j]; p < Ap[j + 1]; p++) adji.push_back(n + Ai[p]);
-    adjp[j + 1] = (int)adji.size();
-  }
-  for (int k = 0; k < m; k++) {
-    for (int q = Atp[k]; q < Atp[k + 1]; q++) adji.push_back(Ati[q]);
-    adjp[n + k + 1] = (int)adji.size();
-  }
-}
-static void sparse_order(const SparseAdj &G, const int n, std::vector<int> &perm) {
-  const std::vector<int> &adjp = G.p, &adji = G.i;
-  const int LEAF = 24;
-  const size_t hub_deg = std::max<size_t>(48, 10 * (adji.size() / std::max(n, 1) + 1));
-  std::vector<int> part((size_t)n, 0), level((size_t)n, 0), queue((size_t)n);
-  perm.assign((size_t)n, -1);
-  std::vector<int> rest, hubs;
-  for (int j = 0; j < n; j++) { if ((size_t)(adjp[j + 1] - adjp[j]) > hub_deg) { hubs.push_back(j); part[j] = -1; } else rest.push_back(j); }
-  for (size_t k = 0; k < hubs.size(); k++) perm[rest.size() + k] = hubs[k];
-  struct Item { std::vector<int> nodes; int lo; };
-  std::vector<Item> stack;
-  stack.push_back(Item{std::move(rest), 0});
-  int label = 0;
-  /* breadth-first search inside the piece labelled `lab` from `root`: fills queue[0 .. count), level[]; visited vertices get label -lab-2
-   * ... and are restored by the caller */
-  auto bfs = [&](int root, int lab, int vis) -> int {
-    int head = 0, tail = 0;
-    queue[tail++] = root; part[root] = vis; level[root] = 0;
-    while (head < tail) {
-      const int v = queue[head++];
-      for (int e = adjp[v]; e < adjp[v + 1]; e++) { const int u = adji[e]; if (part[u] == lab) { part[u] = vis; level[u] = level[v] + 1; queue[tail++] = u; } }
-    }
-    return tail;
-  };
-  while (!stack.empty()) {
-    Item it = std::move(stack.back());
-    stack.pop_back();
-    std::vector<int> &nodes = it.nodes;
-    const int cnt = (int)nodes.size();
-    if (cnt == 0) continue;
-    if (cnt <= LEAF) { std::sort(nodes.begin(), nodes.end()); for (int k = 0; k < cnt; k++) perm[it.lo + k] = nodes[k]; continue; }
-    const int lab = ++label * 2, vis = lab + 1;
-    for (int v : nodes) part[v] = lab;
-    /* connected components, by smallest vertex */
-    std::sort(nodes.begin(), nodes.end());
-    int got = bfs(nodes[0], lab, vis);
-    if (got < cnt) {
-      int lo = it.lo;
-      std::vector<int> comp(queue.begin(), queue.begin() + got);
-      stack.push_back(Item{std::move(comp), lo}); lo += got;
-      for (int v : nodes) if (part[v] == lab) { got = bfs(v, lab, vis); stack.push_back(Item{std::vector<int>(queue.begin(), queue.begin() + got), lo}); lo += got; }
-      continue;
-    }
-    /* one component: pseudo-peripheral root (two more sweeps from the far end), then its level structure */
-    int root = queue[cnt - 1];
-    for (int sweep = 0; sweep < 2; sweep++) {
-      for (int v : nodes) part[v] = lab;
-      bfs(root, lab, vis);
-      const int far = level[queue[cnt - 1]];
-      int best = queue[cnt - 1];
-      for (int k = cnt - 1; k >= 0 && level[queue[k]] == far; k--) if (adjp[queue[k] + 1] - adjp[queue[k]] < adjp[best + 1] - adjp[best]) best = queue[k];
-      if (sweep == 0) root = best;
-    }
-    const int nlev = level[queue[cnt - 1]] + 1;
-    if (nlev < 3) { for (int k = 0; k < cnt; k++) perm[it.lo + k] = nodes[k]; continue; } /* (nodes is sorted) no separator to be had: natural order */
-    std::vector<int> lsize((size_t)nlev, 0);
-    for (int k = 0; k < cnt; k++) lsize[level[queue[k]]]++;
-    /* separator: the smallest level among those that leave between 30 % and 70 % of the piece in front of them; else the median's level */
-    int sep = -1, before = 0, med = 1;
-    { int acc = 0; for (int l = 0; l < nlev; l++) { if (acc <= cnt / 2) med = l; acc += lsize[l]; } med = std::min(std::max(med, 1), nlev - 2); }
-    for (int l = 0; l < nlev; l++) {
-      if (l >= 1 && l <= nlev - 2 && 10 * before >= 3 * cnt && 10 * before <= 7 * cnt && (sep < 0 || lsize[l] < lsize[sep])) sep = l;
-      before += lsize[l];
-    }
-    if (sep < 0) sep = med;
-    std::vector<int> A, Bn, Sn;
-    for (int k = 0; k < cnt; k++) {
-      const int v = queue[k], l = level[v];
-      if (l < sep) A.push_back(v);
-      else if (l > sep) Bn.push_back(v);
-      else { /* a separator vertex without a neighbour beyond the separator belongs to the first half */
-        bool touches = false;
-        for (int e = adjp[v]; e < adjp[v + 1] && !touches; e++) { const int u = adji[e]; touches = (part[u] == vis && level[u] == sep + 1); }
-        if (touches) Sn.push_back(v); else A.push_back(v);
-      }
-    }
-    std::sort(Sn.begin(), Sn.end());
-    const int na = (int)A.size(), nb2 = (int)Bn.size();
-    for (size_t k = 0; k < Sn.size(); k++) perm[it.lo + na + nb2 + (int)k] = Sn[k];
-    stack.push_back(Item{std::move(A), it.lo});
-    stack.push_back(Item{std::move(Bn), it.lo + na});
-  }
-}
-/* cols(jo, visit) calls visit(i) for the row indices i (original numbering; repeats allowed) of column jo of the matrix to factorise */
-template <class Cols>
-static int sparse_analyze(const int n, const Cols &cols, SparseSym &S, size_t max_nnz, std::string &why) {
-  if (S.perm.size() != (size_t)n) { S.perm.resize((size_t)n); for (int j = 0; j < n; j++) S.perm[j] = j; }
-  S.iperm.assign((size_t)n, 0);
-  for (int j = 0; j < n; j++) S.iperm[S.perm[j]] = j;
-  const int *perm = S.perm.data(), *ip = S.iperm.data();
-  S.Lp.assign((size_t)n + 1, 0);
-  S.Li.clear();
-  std::vector<int> parent((size_t)n, -1), mark((size_t)n, -1), child_head((size_t)n, -1), child_next((size_t)n, -1), col;
-  for (int j = 0; j < n; j++) { /* column j of P H P' = column perm[j] of H, rows renumbered */
-    col.clear();
-    mark[j] = j;
-    cols(perm[j], [&](const int io) { const int i = ip[io]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } });
-    for (int c = child_head[j]; c >= 0; c = child_next[c])
-      for (int e = S.Lp[c]; e < S.Lp[c + 1]; e++) { const int i = S.Li[e]; if (i > j && mark[i] != j) { mark[i] = j; col.push_back(i); } }
-    std::sort(col.begin(), col.end());
-    if (S.Li.size() + col.size() > max_nnz) { why = "the sparse factor would hold more than " + std::to_string(max_nnz) + " entries"; return 1; }
-    S.Li.insert(S.Li.end(), col.begin(), col.end());
-    S.Lp[j + 1] = (int)S.Li.size();
-    if (!col.empty()) { parent[j] = col[0]; child_next[j] = child_head[col[0]]; child_head[col[0]] = j; }
-  }
-  const size_t nz = S.Li.size();
-  /* the same entries by rows: columns ascending inside a row because the columns are walked in ascending order */
-  S.Rp.assign((size_t)n + 1, 0);
-  for (size_t e = 0; e < nz; e++) S.Rp[S.Li[e] + 1]++;
-  for (int i = 0; i < n; i++) S.Rp[i + 1] += S.Rp[i];
-  S.Rk.resize(nz); S.Rpos.resize(nz);
-  { std::vector<int> cur(S.Rp.begin(), S.Rp.end() - 1);
-    for (int k = 0; k < n; k++)
-      for (int e = S.Lp[k]; e < S.Lp[k + 1]; e++) { const int dst = cur[S.Li[e]]++; S.Rk[dst] = k; S.Rpos[dst] = e; } }
-  /* levels: height above the leaves (children before parents: a child's index is smaller than its parent's) */
-  std::vector<int> level((size_t)n, 0);
-  int nlev = 0;
-  for (int j = 0; j < n; j++) {
-    if (parent[j] >= 0 && level[parent[j]] < level[j] + 1) level[parent[j]] = level[j] + 1;
-    if (level[j] + 1 > nlev) nlev = level[j] + 1;
-  }
-  S.nlev = nlev;
-  S.levptr.assign((size_t)nlev + 1, 0);
-  for (int j = 0; j < n; j++) S.levptr[level[j] + 1]++;
-  for (int l = 0; l < nlev; l++) S.levptr[l + 1] += S.levptr[l];
-  S.levcol.resize((size_t)n);
-  { std::vector<int> cur(S.levptr.begin(), S.levptr.end() - 1);
-    for (int j = 0; j < n; j++) S.levcol[cur[level[j]]++] = j; }
-  return 0;
-}
-/* Sparse coop mode: the launch plan of one member from the level sets of its elimination tree (patterns only: qpg_batch_update_Q_A leaves it valid).
- * Consecutive levels that one workgroup finishes in one round (at most `round_f` columns for the factorisation, `round_s` rows for the solves) become ONE
- * launch on one workgroup, which runs the one-workgroup loop with its barriers -- a band under the natural ordering (n one-column levels) is one launch;
- * a wider level is a launch of its own on min(G, ceil(width / round)) workgroups, grid-strided where it is wider than the grid.  G = 1 (no memory for
- * a second workgroup's work vectors): one launch per phase. */
-static void sparse_coop_plan(const std::vector<int> &levptr, int nlev, int n, int round_f, int round_s, int G, qpg_batch::SpPlan &P) {
-  auto cut = [&](int round, std::vector<qpg_batch::SpLaunch> &out) {
-    out.clear();
-    if (G <= 1) round = 0x7fffffff; /* no grid to spread a level over: the whole phase is one launch of the one-workgroup loop, not a launch per wide level */
-    for (int l = 0; l < nlev;) {
-      const int w = levptr[(size_t)l + 1] - levptr[(size_t)l];
-      if (w > round) { out.push_back({l, l + 1, std::min(G, (w + round - 1) / round)}); l++; continue; }
-      int l1 = l + 1;
-      while (l1 < nlev && levptr[(size_t)l1 + 1] - levptr[(size_t)l1] <= round) l1++;
-      out.push_back({l, l1, 1});
-      l = l1;
-    }
-  };
-  cut(round_f, P.factor);
-  cut(round_s, P.solve);
-  P.vec_grid = std::max(1, std::min(G, (n + round_s - 1) / round_s));
-  /* permute in, forward launches, D, backward launches; level 0 on a grid: the permutation back is a launch of its own */
-  P.solve_launches = 2 + 2 * (int)P.solve.size() + ((!P.solve.empty() && P.solve[0].grid > 1) ? 1 : 0);
-  P.max_grid = P.vec_grid;
-  for (auto &l : P.factor) P.max_grid = std::max(P.max_grid, l.grid);
-  for (auto &l : P.solve) P.max_grid = std::max(P.max_grid, l.grid);
+  return SparsePattern{P.n, P.m, bt->harr<int>(H_AP, b), bt->harr<int>(H_AI, b), bt->harr<int>(H_ATP, b), bt->harr<int>(H_ATI, b),
+                       bt->harr<int>(H_QFP, b), bt->harr<int>(H_QFI, b)};
 }
 /* analysis of every member (host threads), one device block for the symbolic arrays of all members and the values / work vectors of
  * all slots, upload */
@@ -893,38 +572,7 @@ static int sparse_setup(qpg_batch *bt) {
   const size_t max_nnz = (size_t)1 << 30; /* int32 positions; 8 GB of values per slot */
   const int ordering = bt->ctx->sparse_ordering;
   const bool kkt = bt->kkt != 0;
-  parallel_for(B, [&](size_t b) {
-    sym[b].dissected = false;
-    const HostProblem &P = bt->probs[b];
-    if (kkt) {
-      /* K_full: nested dissection unless the natural order [x; y] is asked for (under [x; y] a banded Q fills the whole constraint block:
-       * about n m entries); the dense rows of A are high-degree vertices, set aside and ordered last */
-      SparseAdj G;
-      sparse_adj_K(bt, b, G);
-      const int nf = P.n + P.m;
-      if (ordering != 0) { sparse_order(G, nf, sym[b].perm); sym[b].dissected = true; }
-      auto cols = [&G](const int jo, auto &&visit) { for (int e = G.p[jo]; e < G.p[jo + 1]; e++) visit(G.i[e]); };
-      rc[b] = sparse_analyze(nf, cols, sym[b], max_nnz, why[b]);
-      return;
-    }
-    const int *Ap = bt->harr<int>(H_AP, b), *Ai = bt->harr<int>(H_AI, b), *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b);
-    const int *Qfp = bt->harr<int>(H_QFP, b), *Qfi = bt->harr<int>(H_QFI, b);
-    auto cols = [=](const int jo, auto &&visit) { /* H = Q + A'A with ALL rows of A */
-      for (int k = Qfp[jo]; k < Qfp[jo + 1]; k++) visit(Qfi[k]);
-      for (int p = Ap[jo]; p < Ap[jo + 1]; p++) { const int t = Ai[p]; for (int q = Atp[t]; q < Atp[t + 1]; q++) visit(Ati[q]); }
-    };
-    if (ordering != 1) rc[b] = sparse_analyze(P.n, cols, sym[b], max_nnz, why[b]); /* natural ordering */
-    const bool deep = ordering == 1 || (ordering < 0 && rc[b] == 0 && sym[b].nlev > 256 && (size_t)sym[b].nlev * 8 > (size_t)P.n);
-    if (!deep) return;
-    SparseSym nd;
-    { SparseAdj G; sparse_adj_H(bt, b, G); sparse_order(G, P.n, nd.perm); }
-    std::string why_nd;
-    const int rc_nd = sparse_analyze(P.n, cols, nd, max_nnz, why_nd);
-    nd.dissected = true;
-    /* automatic: kept when the tree is at least four times shallower and the factor at most three times larger */
-    if (ordering == 1) { rc[b] = rc_nd; why[b] = why_nd; sym[b] = std::move(nd); }
-    else if (rc_nd == 0 && (size_t)nd.nlev * 4 <= (size_t)sym[b].nlev && nd.Li.size() <= 3 * sym[b].Li.size() + (size_t)bt->probs[b].n) sym[b] = std::move(nd);
-  });
+  parallel_for(B, [&](size_t b) { rc[b] = sparse_symbolic(member_pattern(bt, b), kkt, ordering, max_nnz, sym[b], why[b]); });
   for (size_t b = 0; b < B; b++) if (rc[b]) return fail(QPG_ERR_UNSUPPORTED, "qpg_batch_setup: member " + std::to_string(b) + ": " + why[b]);
   size_t nzmax = 1;
   bt->sp_nnz.assign(B, 0); bt->sp_levels.assign(B, 0); bt->sp_perm.assign(B * n, 0);
@@ -977,22 +625,11 @@ static int sparse_setup(qpg_batch *bt) {
   for (size_t b = 0; b < B; b++) {
     const SparseSym &S = sym[b];
     nlev[b] = S.nlev;
-    { /* the index arrays the factor reads, in the factor's numbering: rows of A, columns of the full Q, and each row's first path column */
-      const HostProblem &P = bt->probs[b];
-      const int *Atp = bt->harr<int>(H_ATP, b), *Ati = bt->harr<int>(H_ATI, b), *Qfi = bt->harr<int>(H_QFI, b);
-      const int *ip = S.iperm.data();
-      std::fill(atip.begin(), atip.end(), 0); std::fill(qfip.begin(), qfip.end(), 0); std::fill(first.begin(), first.end(), 0);
-      for (int t = 0; t < P.m; t++) {
-        int f = P.n;
-        for (int q = Atp[t]; q < Atp[t + 1]; q++) { atip[(size_t)q] = ip[Ati[q]]; f = std::min(f, ip[Ati[q]]); }
-        first[(size_t)t] = kkt ? ip[P.n + t] : f; /* KKT mode: the constraint's own row / column of K in the factor's numbering */
-      }
-      for (int k = 0; k < P.nzQf; k++) qfip[(size_t)k] = ip[Qfi[k]];
-      RT_MEMCPY_H2D(V.sp_perm + b * n, bt->sp_perm.data() + b * n, n * 4);
-      RT_MEMCPY_H2D(V.sp_AtiP + b * zA, atip.data(), zA * 4);
-      RT_MEMCPY_H2D(V.sp_QfiP + b * zF, qfip.data(), zF * 4);
-      RT_MEMCPY_H2D(V.sp_first + b * m, first.data(), m * 4);
-    }
+    sparse_factor_index(member_pattern(bt, b), S, kkt, atip, qfip, first);
+    RT_MEMCPY_H2D(V.sp_perm + b * n, bt->sp_perm.data() + b * n, n * 4);
+    RT_MEMCPY_H2D(V.sp_AtiP + b * zA, atip.data(), zA * 4);
+    RT_MEMCPY_H2D(V.sp_QfiP + b * zF, qfip.data(), zF * 4);
+    RT_MEMCPY_H2D(V.sp_first + b * m, first.data(), m * 4);
     RT_MEMCPY_H2D(V.sp_Lp + b * (n + 1), S.Lp.data(), S.Lp.size() * 4);
     if (!S.Li.empty()) {
       RT_MEMCPY_H2D(V.sp_Li + b * nzmax, S.Li.data(), S.Li.size() * 4);
@@ -1256,16 +893,10 @@ static int launch_solve_kernel(qpg_batch *bt, const qpg_view &V_, int budget, in
     return QPG_OK;
   }
   if (!ms_out) { /* coop mode: thousands of short launches per solve, no event pair around each */
-    if (rpt <= 1) BT_LAUNCH(bt, k_solve<1>, grid, shm, V, budget, dynamic);
-    else if (rpt <= 2) BT_LAUNCH(bt, k_solve<2>, grid, shm, V, budget, dynamic);
-    else if (rpt <= 4) BT_LAUNCH(bt, k_solve<4>, grid, shm, V, budget, dynamic);
-    else BT_LAUNCH(bt, k_solve<0>, grid, shm, V, budget, dynamic);
+    BT_RPT(rpt, R, BT_LAUNCH(bt, k_solve<R>, grid, shm, V, budget, dynamic));
     return QPG_OK;
   }
-  if (rpt <= 1) BT_TIMED_LAUNCH(ms, bt, k_solve<1>, grid, shm, V, budget, dynamic);
-  else if (rpt <= 2) BT_TIMED_LAUNCH(ms, bt, k_solve<2>, grid, shm, V, budget, dynamic);
-  else if (rpt <= 4) BT_TIMED_LAUNCH(ms, bt, k_solve<4>, grid, shm, V, budget, dynamic);
-  else BT_TIMED_LAUNCH(ms, bt, k_solve<0>, grid, shm, V, budget, dynamic);
+  BT_RPT(rpt, R, BT_TIMED_LAUNCH(ms, bt, k_solve<R>, grid, shm, V, budget, dynamic));
   if (ms_out) *ms_out = ms;
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_solve failed: " + std::string(RT_LAST_ERROR()));
   return QPG_OK;
@@ -1320,7 +951,7 @@ template <class F> static void co_chain(qpg_batch *bt, int key, F issue) {
 static int coop_grid(const qpg_batch *bt) { return std::max(8, std::min(bt->ctx->coop_workgroups, 1024 / std::max(1, bt->B))); }
 static int coop_linear_algebra(qpg_batch *bt, const qpg_view &V, int b, const qpg_scalars &sc) {
   if (bt->sparse) { /* sparse coop mode: the member's plan, launch by launch (chains 0 / 1: the factorisation into the factor / LD_Q, 2: the solve) */
-    const qpg_batch::SpPlan &P = bt->sp_plan[(size_t)b];
+    const SpPlan &P = bt->sp_plan[(size_t)b];
     const int slot = b;
     {
       char sig[200];
@@ -2246,12 +1877,7 @@ static int run_op(qpg_batch *bt, qpg_int idx, int op, const char *fn) {
   }
   if (bt->sparse && op != QP_OP_MATVEC_A && op != QP_OP_MATVEC_Q && op != QP_OP_MATTVEC_A && op != QP_OP_RESIDUALS && op != QP_OP_ACTIVE && op != QP_OP_LINESEARCH)
     return fail(QPG_ERR_UNSUPPORTED, std::string(fn) + ": works on the dense panel (this batch keeps a sparse L D L')");
-  auto own = [&](int o) { /* the operation on the QP's own workgroup */
-    if (rpt <= 1) BT_LAUNCH(bt, k_op<1>, 1, shm, bt->V, (int)idx, o);
-    else if (rpt <= 2) BT_LAUNCH(bt, k_op<2>, 1, shm, bt->V, (int)idx, o);
-    else if (rpt <= 4) BT_LAUNCH(bt, k_op<4>, 1, shm, bt->V, (int)idx, o);
-    else BT_LAUNCH(bt, k_op<0>, 1, shm, bt->V, (int)idx, o);
-  };
+  auto own = [&](int o) { BT_RPT(rpt, R, BT_LAUNCH(bt, k_op<R>, 1, shm, bt->V, (int)idx, o)); }; /* the operation on the QP's own workgroup */
   const bool factor_op = op == QP_OP_LDLCHOL || op == QP_OP_LDLCHOL_QATSA || op == QP_OP_SOLVE;
   const bool update_op = op == QP_OP_UPDATE_ENTER || op == QP_OP_DOWNDATE_LEAVE || op == QP_OP_UPDATE_SIGMA;
   if ((factor_op || (update_op && bt->ctx->coop_updates != 0)) && coop_wanted(bt)) {
@@ -2425,10 +2051,7 @@ extern "C" int qpg_batch_sweep_probe(qpg_batch *bt, qpg_int reps, qpg_int nranks
   const int rpt = (bt->nfac + bt->threads - 1) / bt->threads;
   const size_t shm = (size_t)bt->lds_bytes;
   float ms = 0.f;
-  if (rpt <= 1) BT_TIMED_LAUNCH(ms, bt, k_sweep_probe<1>, grid, shm, bt->V, (int)reps, (int)nranks);
-  else if (rpt <= 2) BT_TIMED_LAUNCH(ms, bt, k_sweep_probe<2>, grid, shm, bt->V, (int)reps, (int)nranks);
-  else if (rpt <= 4) BT_TIMED_LAUNCH(ms, bt, k_sweep_probe<4>, grid, shm, bt->V, (int)reps, (int)nranks);
-  else BT_TIMED_LAUNCH(ms, bt, k_sweep_probe<0>, grid, shm, bt->V, (int)reps, (int)nranks);
+  BT_RPT(rpt, R, BT_TIMED_LAUNCH(ms, bt, k_sweep_probe<R>, grid, shm, bt->V, (int)reps, (int)nranks));
   if (RT_SYNC() != 0) return fail(QPG_ERR_RUNTIME, "k_sweep_probe failed: " + std::string(RT_LAST_ERROR()));
   if (ms_out) *ms_out = ms;
   return api_ok();

@@ -744,7 +744,7 @@ __global__ __launch_bounds__(QP_T) QP_OCCUPANCY void k_co_solve(qpg_view V, int 
   else { for (int i = blockIdx.x * QP_T + threadIdx.x; i < n; i += QP_T * gridDim.x) a.d()[i] = a.temp_n()[i]; }
 }
 
-/* ---- sparse coop mode (context option "sparse_coop"; qpalm_capi.inc: sparse_coop_plan): the sparse L D L' of ONE QP on many workgroups.  The launch
+/* ---- sparse coop mode (context option "sparse_coop"; qpalm_host_symbolic.h: sparse_coop_plan): the sparse L D L' of ONE QP on many workgroups.  The launch
  * plan cuts the levels of the elimination tree into launches: a level wider than one workgroup's round is a launch of its own on a grid (its columns /
  * rows grid-strided), a run of narrower levels one launch on one workgroup.  What differs between two calls of a recorded chain is read from the QP's
  * scalars (pend_la: with or without A' Sigma A; the proximal term; pend_gam), not passed as an argument. ---- */

@@ -5,12 +5,12 @@
  * CHOLMOD's analyze + factorize + solve) for QPs whose Schur complement is sparse or has more rows than a dense panel allows
  * (8192): device memory per QP is proportional to nnz(L), not n^2.
  *
- *  - Symbolic analysis once per QP on the host (qpalm_capi.inc: sparse_analyze): pattern of Q + A'A with ALL rows of A (a superset
+ *  - Symbolic analysis once per QP on the host (qpalm_host_symbolic.h: sparse_analyze): pattern of Q + A'A with ALL rows of A (a superset
  *    of every active set's pattern, so the structure never changes while constraints enter and leave), elimination tree, pattern of
  *    L by columns (strict lower part, rows ascending), the same entries by rows (column + position in the column arrays, columns
  *    ascending) and the level sets of the elimination tree.  Natural ordering: what the reference configures
  *    (solver_interface.c:530-540, c->nmethods = 1, method[0].ordering = CHOLMOD_NATURAL) -- or, context option "sparse_ordering", a
- *    nested dissection (qpalm_capi.inc: sparse_order) under which the factor is that of P H P': the kernels below then work in the
+ *    nested dissection (qpalm_host_symbolic.h: sparse_order) under which the factor is that of P H P': the kernels below then work in the
  *    permuted numbering (perm, AtiP, QfiP, first) and the solve permutes its right-hand side in and out.
  *  - Numeric factorisation: left-looking by columns, the columns of one level of the elimination tree in parallel (one wavefront
  *    per column, lanes over the entries), a level ends with a workgroup barrier.  A column is assembled AND updated in a dense work

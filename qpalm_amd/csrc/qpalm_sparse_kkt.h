@@ -6,7 +6,7 @@
  *   kkt_solve + iterative refinement                                    src/solver_interface.c:238-247, newton.c:55-90
  *
  * K = [[Q + I/gamma, A_a'], [A_a, -Sigma_a^{-1}]] of n + m rows, inactive constraints = unit rows, as P K P' = L D L' on the pattern of
- * K_full (every row of A present: qpalm_capi.inc, sparse_adj_K), the pattern the reference's kkt_full gives LADEL.  The ordering is a nested
+ * K_full (every row of A present: qpalm_host_symbolic.h, sparse_adj_K), the pattern the reference's kkt_full gives LADEL.  The ordering is a nested
  * dissection of K's graph with the dense rows of A last (or the natural [x; y], "sparse_ordering" = 0).  D has mixed signs (K is
  * quasi-definite); nothing here divides by anything but a pivot.
  *  - Form + factorise: sp_factor<true> (qpalm_sparse.h), K assembled column by column inside the left-looking level-parallel factorisation.

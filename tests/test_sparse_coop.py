@@ -1,6 +1,6 @@
 """Sparse coop mode (context option "sparse_coop" = 1): the sparse L D L' of ONE QP factorised and solved on many workgroups -- what the reference hands
 to CHOLMOD's factorize and solve (src/solver_interface.c:319-370, 505-519).  The levels of the elimination tree become a chain of launches
-(qpalm_capi.inc: sparse_coop_plan; kernels k_co_sp_factor / k_co_sp_solve): a level wider than one workgroup's round runs on a grid, a run of narrower
+(qpalm_host_symbolic.h: sparse_coop_plan; kernels k_co_sp_factor / k_co_sp_solve): a level wider than one workgroup's round runs on a grid, a run of narrower
 levels on one workgroup.  No column's arithmetic depends on the workgroup that computes it, so the yardstick is exact: the same build with
 "sparse_coop" = 0 -- x, y, objective and dual objective BIT FOR BIT, status, iteration counts and the factorisation / update / solve counters equal --
 and, beside it, the oracle in its sparse-storage mode as tests/test_sparse_factor.py sets it up (x, y to RTOL).
